@@ -1,8 +1,14 @@
 #!/usr/bin/env python3
 """bench.py -- denoising steps/s of the rule-guided sampling hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ... bench.py --gpus N ...
+
+A plain run does what the headline needs and nothing else: set-up, W warm-up steps, ONE timed region of exactly K steps, the outputs
+of the last step if --dump-outputs is given, the JSON line.  --full adds everything else listed below (three timed regions, the
+roofline pass, the in-situ counters and power, fp32_exact, scg, uint8_flips, cpu_baseline).
+--dump-outputs DIR: the dict the last timed step's sampler call returned (sample, pred_xstart) as DIR/<name>.npy in float32; the
+weights and the Philox noise are seeded, so the same arguments give the same inputs in every run.
 
 `python bench.py --gpus N` with N > 1 and no torchrun environment re-executes itself through torch.distributed.run with N
 ranks on 127.0.0.1 (and fails loudly when the box has fewer than N devices); `n_gpus` in the JSON is the RCCL world size
@@ -11,15 +17,16 @@ that actually ran.
 Metric (BASELINE.json): denoising steps/sec, whole node, DiTRotary_XL_8 on 4x128x16 latents.
 Headline workload = BASELINE config[1] ("C2"): unconditional DDIM-50 (eta=1) on a batch of 16 latents per GPU, one "step" =
 one ddim_sample call over that batch (eps-network forward + fused step update + Philox noise).  W untimed warm-up steps,
-then three timed regions of exactly K steps each, each bracketed by barrier + device synchronise, MAX over ranks per
-region; `value` / `ms_per_step` are the MEDIAN region (all three are listed in config.repeats_ms_per_step).  For N > 1 every
+then timed regions of exactly K steps each (one in a plain run, three under --full, --repeats to choose), each bracketed by
+barrier + device synchronise, MAX over ranks per region; `value` / `ms_per_step` are the MEDIAN region (all of them are listed
+in config.repeats_ms_per_step).  For N > 1 every
 rank runs its own batch-16 chain (the path shards over samples; no data-path collective): scaling = weak.
 Nothing of a step is skipped or carried over: the one thing the sampler computes for several steps at once -- the adaLN modulation rows of
 the schedule's next timesteps, one pass over those weights per 32 rows (guided_diffusion/dit.py cond_hint; bit-identical chains) -- is
 dropped at the start of every timed region, so each region pays the passes its K steps need (config.cond_ahead counts them;
 RGM_COND_AHEAD=0 runs the pass in every forward).
 
-One JSON line on stdout (rank 0) per the driver contract, plus
+One JSON line on stdout (rank 0) per the driver contract, plus under --full
   roofline     : the dominant kernel of the headline run (pre-split bf16x3 GEMM) -- algorithmic 2MNK FLOPs of its launches
                  divided by their HIP-event durations measured live on the launch stream (separate 2-step pass with
                  rgm_prof_enable, same workload), against 2500 / 3 TFLOP/s (dense bf16 MFMA peak, 3 MFMAs per product);
@@ -104,6 +111,7 @@ class C2Workload:
         out = self.d.ddim_sample(self.fn, self.x, t, clip_denoised=False, model_kwargs={}, eta=1.0)
         self.d._t_host = None
         self.x = out["sample"]
+        self.last = out
 
 
 class SCGWorkload:
@@ -163,6 +171,7 @@ class SCGWorkload:
                               scale_factor=1.2465, guidance_kwargs=self.guid, scg_kwargs=self.scg)
         self.d._t_host = None
         self.x = out["sample"]
+        self.last = out
 
 
 class LongWorkload(SCGWorkload):
@@ -230,6 +239,7 @@ class C3Workload:
                               guidance_kwargs=self.guid)
         self.d._t_host = None
         self.x = out["sample"]
+        self.last = out
 
 
 class DPSRuleWorkload(SCGWorkload):
@@ -260,6 +270,7 @@ class DPSRuleWorkload(SCGWorkload):
                               embed_model=self.vae, scale_factor=1.2465, guidance_kwargs=self.guid)
         self.d._t_host = None
         self.x = out["sample"]
+        self.last = out
 
 
 def roofline_pass(work, steps=2):
@@ -511,6 +522,27 @@ def eps_networks(work):
     return [v for v in vars(work).values() if isinstance(v, DiTRotary)]
 
 
+DUMP_BYTES = 64 * 2 ** 20
+
+
+def dump_outputs(out, path):
+    """The tensors of the sampler's return value (the last timed step) -> path/<name>.npy: float32 (float64 stays float64, integer
+    tensors become float64).  An array over its share of DUMP_BYTES is cut to a fixed, seeded sample of its entries (flat, sorted)."""
+    arrs = {}
+    for k, v in out.items():
+        if torch.is_tensor(v):
+            wide = v.dtype == torch.float64 or not v.is_floating_point()
+            arrs[k] = v.detach().to(torch.float64 if wide else torch.float32).cpu().numpy()
+    os.makedirs(path, exist_ok=True)
+    share = DUMP_BYTES // max(1, len(arrs))
+    for k, a in arrs.items():
+        if a.nbytes > share:
+            keep = np.sort(np.random.RandomState(0).choice(a.size, share // a.itemsize, replace=False))
+            a = a.reshape(-1)[keep]
+        np.save(os.path.join(path, k + ".npy"), a)
+    return sorted(arrs)
+
+
 def time_steps(work, steps, world, dist):
     """One timed region of exactly `steps` steps: barrier + synchronise on both sides, MAX over ranks.  Conditioning rows computed ahead
     (guided_diffusion/dit.py cond_hint: one pass over the adaLN weights serves the next 32 (t, y) rows of the schedule) are dropped first:
@@ -628,11 +660,16 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--batch", type=int, default=None)
     ap.add_argument("--workload", default="c2", choices=["c2", "c3", "scg", "long", "dps_rule"])
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="headline + roofline only (skip fp32_exact, scg, uint8_flips, cpu_baseline)")
-    ap.add_argument("--repeats", type=int, default=3, help="timed regions of --steps steps each; the median is reported")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline: three timed regions, roofline (+ in-situ counters, power), fp32_exact, scg, "
+                         "uint8_flips, cpu_baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (sample, pred_xstart) as DIR/<name>.npy, float32")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip cpu_baseline")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: headline + roofline only (skip fp32_exact, scg, uint8_flips, cpu_baseline)")
+    ap.add_argument("--repeats", type=int, default=None, help="timed regions of --steps steps each, the median is reported (default: 1, with --full 3)")
     ap.add_argument("--traffic-child", action="store_true", help=argparse.SUPPRESS)   # internal: the profiled child of measure_traffic
-    ap.add_argument("--no-traffic", action="store_true", help="skip the in-situ rocprofv3 --pmc passes (roofline.traffic from profiles/traffic.json)")
+    ap.add_argument("--no-traffic", action="store_true", help="with --full: skip the in-situ rocprofv3 --pmc passes (roofline.traffic from profiles/traffic.json)")
     ap.add_argument("--simulate-ranks", type=int, default=0,
                     help="--workload scg on ONE GPU: time the per-rank work of an R-GPU run (this process scores candidates "
                          "[0, n/R) like rank 0 would, the all-gather is a local stand-in): an estimate of the sharded step "
@@ -695,15 +732,19 @@ def main():
         return
     for m in eps_networks(work):
         m.ahead_passes = 0
-    regions = [time_steps(work, args.steps, world, dist) for _ in range(max(1, args.repeats))]
+    repeats = args.repeats if args.repeats is not None else (3 if args.full else 1)
+    regions = [time_steps(work, args.steps, world, dist) for _ in range(max(1, repeats))]
     ahead_passes = sum(getattr(m, "ahead_passes", 0) for m in eps_networks(work))
     order = sorted(range(len(regions)), key=lambda i: regions[i][0])
     dt, gpu_ms = regions[order[len(order) // 2]]
-    try:                                                         # every rank runs it (SCG steps hold a collective)
-        roof = roofline_pass(work)
-    except Exception as e:                                       # never lose the headline number
-        log("roofline pass failed:", repr(e))
-        roof = None
+    if args.dump_outputs and rank == 0:                          # before --full's passes run more steps on the same workload
+        log("bench.py: outputs of the last timed step ->", ", ".join(dump_outputs(work.last, args.dump_outputs)))
+    roof = None
+    if args.full:
+        try:                                                     # every rank runs it (SCG steps hold a collective)
+            roof = roofline_pass(work)
+        except Exception as e:                                   # never lose the headline number
+            log("roofline pass failed:", repr(e))
 
     if roof is not None and rank == 0 and world == 1 and not args.no_traffic and not args.no_extras and args.simulate_ranks <= 1:
         try:
@@ -729,7 +770,7 @@ def main():
             # the same fraction against the MFMA peak at the clock the board sustained over the whole step (nominal peak: 2.4 GHz)
             roof["frac_at_sustained_clock"] = round(roof["frac"] * 2400.0 / max(pw["sclk_mhz_median"], 1.0), 4)
     extras = {}
-    if args.workload == "c2" and not args.no_extras and args.simulate_ranks <= 1:
+    if args.full and args.workload == "c2" and not args.no_extras and args.simulate_ranks <= 1:
         def attempt(name, fn):
             try:
                 extras[name] = fn()
@@ -758,7 +799,7 @@ def main():
             if world == 1 and not args.no_cpu_baseline:
                 attempt("cpu_baseline", lambda: cpu_baseline(work))
     same_winners = None
-    if world > 1 and args.workload in ("scg", "long"):
+    if args.full and world > 1 and args.workload in ("scg", "long"):
         # every rank must have picked the same candidates in the last step (identical gathered table -> identical first-argmax)
         mine = work.d.last_scg["max_ind"].to(torch.int64).contiguous()
         allm = [torch.empty_like(mine) for _ in range(world)]
@@ -780,7 +821,8 @@ def main():
             "config": {"workload": work.name + (f" [SIMULATED rank 0 of {args.simulate_ranks}: per-rank work only, no fabric]"
                                                 if args.simulate_ranks > 1 else ""), "batch_per_gpu": batch, "sample_steps_per_s": round(units * batch / dt, 2),
                        "weights": "synthetic random-init (rgm.synth seed 1; adaLN/final layers re-randomised)",
-                       "timing": f"median of {len(regions)} timed regions of {args.steps} steps",
+                       "timing": (f"median of {len(regions)} timed regions of {args.steps} steps" if len(regions) > 1
+                                  else f"one timed region of {args.steps} steps"),
                        "repeats_ms_per_step": [round(1e3 * r[0] / args.steps, 3) for r in regions],
                        "gpu_ms_per_step_events": round(gpu_ms / args.steps, 3),
                        # adaLN conditioning ahead of the step (guided_diffusion/dit.py): rows per pass over the adaLN weights (0 = every forward
@@ -800,7 +842,8 @@ def main():
             res["config"]["same_winners_on_every_rank"] = bool(same_winners)
         if "uint8_flips" in extras:
             res["config"]["uint8_flips"] = extras.pop("uint8_flips")
-        res["roofline"] = roof
+        if args.full:
+            res["roofline"] = roof
         for k in ("fp32_exact", "scg", "c3_batch_sharded", "cpu_baseline"):
             if k in extras:
                 res[k] = extras[k]

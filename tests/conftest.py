@@ -1,4 +1,5 @@
 """pytest wiring: `gpu` marker, import paths, golden-fixture loader."""
+import glob
 import os
 import sys
 import numpy as np
@@ -31,7 +32,11 @@ def pytest_collection_modifyitems(config, items):
 
 
 def load_golden(name):
-    return dict(np.load(os.path.join(GOLDEN, name + ".npz")))
+    """tests/golden/<name>.npz, joined with <name>.part2.npz, ... where make_golden.py stored a fixture in parts (no file over 1 MiB)"""
+    out = dict(np.load(os.path.join(GOLDEN, name + ".npz")))
+    for part in sorted(glob.glob(os.path.join(GOLDEN, name + ".part*.npz"))):
+        out.update(np.load(part))
+    return out
 
 
 @pytest.fixture(scope="session")

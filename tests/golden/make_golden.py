@@ -10,6 +10,8 @@ numpy RandomState seeds (frozen stream) -- both reproducible on the GPU box.
 Noise is teacher-forced: the reference's th.randn / th.randn_like are fed from a queue so that
 the draw order of gaussian_diffusion.py (:846, :699/:715/:944, :512) is reproduced exactly.
 """
+import glob
+import io
 import os
 import sys
 import time
@@ -46,11 +48,36 @@ def err(name, a, b):
     return r
 
 
+PART_BYTES = 960 * 1024
+
+
 def save(name, **arrs):
     stored = {k: int(v) for k, v in arrs.items() if k.endswith("seed") and np.ndim(v) == 0}
     assert stored == FIXTURE_SEEDS.get(name, {}), f"{name}: stored seeds {stored} != FIXTURE_SEEDS[{name!r}] {FIXTURE_SEEDS.get(name, {})}"
+    for old in glob.glob(os.path.join(HERE, name + ".part*.npz")):
+        os.remove(old)
     p = os.path.join(HERE, name + ".npz")
     np.savez_compressed(p, **arrs)
+    if os.path.getsize(p) > PART_BYTES:
+        # no committed file over 1 MiB: the seeds and the first arrays stay in name.npz, the rest goes to name.part2.npz, name.part3.npz,
+        # ... (conftest.load_golden joins them), each filled up to PART_BYTES of compressed arrays
+        def packed(a):
+            b = io.BytesIO()
+            np.savez_compressed(b, a=a)
+            return b.tell()
+        parts = [{k: v for k, v in arrs.items() if k.endswith("seed")}]
+        size = sum(packed(v) for v in parts[0].values())
+        for k, v in arrs.items():
+            if k in parts[0]:
+                continue
+            n = packed(v)
+            if size + n > PART_BYTES and len(parts[-1]) > 0:
+                parts.append({})
+                size = 0
+            parts[-1][k] = v
+            size += n
+        for i, part in enumerate(parts):
+            np.savez_compressed(p if i == 0 else os.path.join(HERE, f"{name}.part{i + 1}.npz"), **part)
     print(f"  wrote {name}.npz  {os.path.getsize(p) / 1024:.1f} KiB")
 
 

@@ -580,7 +580,7 @@ def test_two_rank_scg_bench_control_flow_on_one_device():
     import json, os, subprocess, sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, RGM_BENCH_ONE_DEVICE="1")
-    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--no-extras", "--workload", "scg", "--steps", "2",
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--full", "--no-extras", "--workload", "scg", "--steps", "2",
                           "--warmup", "1", "--repeats", "1"], capture_output=True, text=True, timeout=1500, cwd=root, env=env)
     assert out.returncode == 0, out.stderr[-2000:]
     line = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
@@ -619,7 +619,7 @@ def test_eight_rank_scg_bench_control_flow_on_one_device():
     import json, os, subprocess, sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, RGM_BENCH_ONE_DEVICE="1")
-    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "8", "--no-extras", "--workload", "scg", "--steps", "2",
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "8", "--full", "--no-extras", "--workload", "scg", "--steps", "2",
                           "--warmup", "1", "--repeats", "1"], capture_output=True, text=True, timeout=2400, cwd=root, env=env)
     assert out.returncode == 0, out.stderr[-2000:]
     line = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
@@ -636,7 +636,7 @@ def test_eight_rank_long_sequence_bench_control_flow_on_one_device():
     import json, os, subprocess, sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, RGM_BENCH_ONE_DEVICE="1")
-    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "8", "--no-extras", "--workload", "long", "--batch", "1", "--steps", "1",
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "8", "--full", "--no-extras", "--workload", "long", "--batch", "1", "--steps", "1",
                           "--warmup", "1", "--repeats", "1"], capture_output=True, text=True, timeout=2400, cwd=root, env=env)
     assert out.returncode == 0, out.stderr[-2000:]
     line = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
@@ -651,7 +651,7 @@ def test_two_gpu_scg_bench_runs_over_rccl_when_the_box_has_two_gpus():
         pytest.skip("needs >= 2 GPUs (RCCL); the gloo two-rank tests in test_host_logic.py cover the protocol on CPU")
     import json, os, subprocess, sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--no-extras", "--workload", "scg", "--steps", "2",
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--full", "--no-extras", "--workload", "scg", "--steps", "2",
                           "--warmup", "1"], capture_output=True, text=True, timeout=1500, cwd=root)
     assert out.returncode == 0, out.stderr[-2000:]
     line = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])

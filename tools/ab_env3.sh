@@ -3,6 +3,6 @@
 VAR=$1; VALS=$2; shift 2
 for i in 1 2 3; do
   for v in $VALS; do
-    env $VAR=$v python bench.py "$@" --no-extras --no-traffic 2>/dev/null | grep '^{"metric' | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('$VAR=$v', d['ms_per_step'], d['config']['repeats_ms_per_step'])"
+    env $VAR=$v python bench.py "$@" --full --no-extras --no-traffic 2>/dev/null | grep '^{"metric' | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('$VAR=$v', d['ms_per_step'], d['config']['repeats_ms_per_step'])"
   done
 done

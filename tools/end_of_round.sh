@@ -7,15 +7,16 @@ R=${1:-r04}
 ROOT=${GRAFT_REPO_ROOT:-/root/repo}
 cd $ROOT
 mkdir -p gpurun_out
-python bench.py --steps 20 --warmup 5 > gpurun_out/${R}_bench_default_n1.json 2> gpurun_out/${R}_bench_default_n1.log
-tools/prof_bench.sh ${R}_c2 --no-extras --steps 20 --warmup 5 > /dev/null 2>&1
-tools/prof_bench.sh ${R}_c3 --no-extras --workload c3 --steps 20 --warmup 5 > /dev/null 2>&1
-tools/prof_bench.sh ${R}_scg_b4_n16 --no-extras --workload scg --steps 5 --warmup 2 > /dev/null 2>&1
-tools/prof_bench.sh ${R}_long_b2 --no-extras --workload long --steps 5 --warmup 2 > /dev/null 2>&1
-tools/prof_bench.sh ${R}_scg_r8 --no-extras --workload scg --simulate-ranks 8 --steps 10 --warmup 3 > /dev/null 2>&1
-tools/prof_bench.sh ${R}_long_b2_r8 --no-extras --workload long --simulate-ranks 8 --steps 5 --warmup 2 > /dev/null 2>&1
-tools/prof_bench.sh ${R}_c2_b4 --no-extras --batch 4 --steps 20 --warmup 5 > /dev/null 2>&1
-tools/prof_bench.sh ${R}_c2_b8 --no-extras --batch 8 --steps 20 --warmup 5 > /dev/null 2>&1
+OUT=$_                # the folder the line above made: every file of this script goes there
+python bench.py --full --steps 20 --warmup 5 > $OUT/${R}_bench_default_n1.json 2> $OUT/${R}_bench_default_n1.log
+tools/prof_bench.sh ${R}_c2 --full --no-extras --steps 20 --warmup 5 > /dev/null 2>&1
+tools/prof_bench.sh ${R}_c3 --full --no-extras --workload c3 --steps 20 --warmup 5 > /dev/null 2>&1
+tools/prof_bench.sh ${R}_scg_b4_n16 --full --no-extras --workload scg --steps 5 --warmup 2 > /dev/null 2>&1
+tools/prof_bench.sh ${R}_long_b2 --full --no-extras --workload long --steps 5 --warmup 2 > /dev/null 2>&1
+tools/prof_bench.sh ${R}_scg_r8 --full --no-extras --workload scg --simulate-ranks 8 --steps 10 --warmup 3 > /dev/null 2>&1
+tools/prof_bench.sh ${R}_long_b2_r8 --full --no-extras --workload long --simulate-ranks 8 --steps 5 --warmup 2 > /dev/null 2>&1
+tools/prof_bench.sh ${R}_c2_b4 --full --no-extras --batch 4 --steps 20 --warmup 5 > /dev/null 2>&1
+tools/prof_bench.sh ${R}_c2_b8 --full --no-extras --batch 8 --steps 20 --warmup 5 > /dev/null 2>&1
 python tools/batch_sweep.py > gpurun_out/${R}_batch_sweep.txt 2>&1
 python tools/cls_time.py 1 4 8 16 32 > gpurun_out/${R}_cls_time.txt 2>&1
 python tools/hazard_soak.py 100 > gpurun_out/${R}_hazard_soak.txt 2>&1

@@ -4,5 +4,5 @@
 for v in ${@:-0 2 0 2}; do
   export RGM_SPLIT_PAIR=$v
   echo "=== RGM_SPLIT_PAIR=$v"
-  python bench.py --steps 20 --warmup 5 --no-extras --no-traffic 2>/dev/null | grep '^{"metric' | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('C2 ms_per_step', d['ms_per_step'])"
+  python bench.py --steps 20 --warmup 5 --full --no-extras --no-traffic 2>/dev/null | grep '^{"metric' | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('C2 ms_per_step', d['ms_per_step'])"
 done

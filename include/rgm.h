@@ -100,7 +100,9 @@ int rgm_layernorm_modulate(const float* x, float* out, int M, int D, float eps, 
  * 16-byte aligned pointers; RGM_ERR_INVALID for any other shape (rgm_dit_forward then runs its tiled GEMM instead). */
 int rgm_adaln_stream(const float* cs, const float* W, const float* bias, float* mod, int N, int D, int L, void* stream);
 /* RotaryAttention core (dit.py:263-277): qkv (N*T, 3*heads*hd) -> o (N*T, heads*hd); rotary on the first
- * 2*rot_half channels of q,k with cos/sin tables (T, rot_half); softmax scale hd^-0.5. hd in {64,72}. */
+ * 2*rot_half channels of q,k with cos/sin tables (T, rot_half); softmax scale hd^-0.5. hd in {64,72}, 1 <= T <= 8192.
+ * A head's K and V stay in LDS up to T = 256 (hd 72) / 288 (hd 64); longer sequences run the streaming (flash-style) kernel,
+ * csrc/attention_stream.hip, in the same arithmetic. */
 int rgm_rotary_attention(const float* qkv, float* o, const float* cos_tab, const float* sin_tab,
                          int N, int T, int heads, int hd, int rot_half, void* stream);
 /* the same forward, also writing lse (N*heads*T): log-sum-exp of the scaled scores of every query, the saved quantity of the backward */
@@ -170,6 +172,9 @@ int rgm_set_dit_halves(int min_batch, int* prev);
  * interleaved Q prologue, which the two-phase prologue removed (profiles/r05_attn_hazard_two_phase_n96.txt).  1 = on,
  * 0 = guard (default).  Returns the previous setting. */
 int rgm_set_attn_pairs(int on);
+/* The streaming attention forward (csrc/attention_stream.hip) for EVERY sequence length of hd 64 / 72, not only where the resident
+ * kernels cannot hold a head: comparisons of the two on the same inputs.  1 = on, 0 = off (default).  Returns the previous setting. */
+int rgm_set_attn_stream(int on);
 /* Deterministic split-K of the pre-split GEMM (csrc/gemm2.hip: K slices as a batch + one fixed-order reduce kernel, which for the fc2
  * of a DiT block also writes the next adaLN-LayerNorm): the scratch is caller memory like every other workspace,
  * rgm_gemm_scratch_bytes(M, N) bytes for GEMMs of up to M rows and N columns, 16-byte aligned, no initialisation.  tile 0 lets the

@@ -5,7 +5,7 @@
 // rotate_queries_or_keys (interleaved pairs on the first `2*rot_half` channels, position = token index).
 //
 // Shape regime: T <= 288 tokens (256 patches, +1 cls token for classifiers, 128 for DiffCollage half
-// windows), head_dim 72 (XL) or 64 (S/B).  The whole K and V of one head fit the 160 KiB LDS of a
+// windows), head_dim 72 (XL) or 64 (S/B); longer sequences go to the streaming kernel (attention_stream.hip).  The whole K and V of one head fit the 160 KiB LDS of a
 // CDNA4 CU (256 x 76 x 4 B + 256 x 72 x 4 B = 148 KiB), so the kernel is single-pass: no online
 // softmax, no rescaling -- each wave keeps the full score strip of its 32 queries in registers.
 //
@@ -23,18 +23,6 @@
 #include "common.h"
 
 namespace rgm {
-
-// exp(x) for x <= 0 without ocml's range-check compares (each costs an SGPR-pair mask; 128 of them
-// per strip spill the scalar file): exp2 of the product x*log2(e) carried in two floats, ~1-2 ulp.
-__device__ __forceinline__ float exp_neg(float x) {
-  const float L2E_HI = 1.44269502162933349609375f, L2E_LO = 1.925963033500011e-8f;
-  x = fmaxf(x, -104.0f);   // masked scores are -inf: (-inf)*c + inf would be NaN below; 2^-150 flushes to exactly 0
-  const float t = x * L2E_HI;
-  float r = fmaf(x, L2E_HI, -t);
-  r = fmaf(x, L2E_LO, r);
-  const float e = __builtin_amdgcn_exp2f(t);
-  return fmaf(e, r * 0.693147182464599609375f, e);
-}
 
 template <int HD, int NKT>
 __global__ __launch_bounds__(512) void rotary_attention_kernel(const float* __restrict__ qkv, float* __restrict__ o,
@@ -216,6 +204,7 @@ static int launch_attn(const float* qkv, float* o, const float* ct, const float*
 
 int rotary_attention_launch(const float* qkv, float* o, const float* cos_tab, const float* sin_tab, int N, int T,
                             int heads, int hd, int rot_half, hipStream_t s, float* lse, int out_split) {
+  if (attn_stream_wanted(T, hd)) return rotary_attention_stream_launch(qkv, o, cos_tab, sin_tab, N, T, heads, hd, rot_half, s, lse, out_split, 0);
   RGM_REQUIRE(N > 0 && T > 0 && T <= 288, "attention: T=%d out of range (1..288)", T);
   RGM_REQUIRE((2 * rot_half) % 4 == 0 && 2 * rot_half <= hd, "attention: rotary dim %d", 2 * rot_half);
   const int nkt = (T + 31) / 32;

@@ -435,6 +435,7 @@ static int launch_attn_x3_blocked(const float* qkv, float* o, const float* ct, c
 // same contract as rotary_attention_launch (attention.hip)
 int rotary_attention_x3_launch(const float* qkv, float* o, const float* cos_tab, const float* sin_tab, int N, int T, int heads,
                                int hd, int rot_half, hipStream_t s, float* lse, int out_split) {
+  if (attn_stream_wanted(T, hd)) return rotary_attention_stream_launch(qkv, o, cos_tab, sin_tab, N, T, heads, hd, rot_half, s, lse, out_split, 1);
   RGM_REQUIRE(N > 0 && T > 0 && T <= 288, "attention: T=%d out of range (1..288)", T);
   RGM_REQUIRE((2 * rot_half) % 4 == 0 && 2 * rot_half <= hd, "attention: rotary dim %d", 2 * rot_half);
   const int nkt = (T + 31) / 32;

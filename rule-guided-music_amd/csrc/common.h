@@ -207,6 +207,17 @@ __device__ __forceinline__ float silu_grad_f(float x) {
   const float sg = 1.0f / (1.0f + expf(-x));
   return sg * (1.0f + x * (1.0f - sg));
 }
+// exp(x) for x <= 0 without ocml's range-check compares (each costs an SGPR-pair mask; 128 of them
+// per strip spill the scalar file): exp2 of the product x*log2(e) carried in two floats, ~1-2 ulp.
+__device__ __forceinline__ float exp_neg(float x) {
+  const float L2E_HI = 1.44269502162933349609375f, L2E_LO = 1.925963033500011e-8f;
+  x = fmaxf(x, -104.0f);   // masked scores are -inf: (-inf)*c + inf would be NaN below; 2^-150 flushes to exactly 0
+  const float t = x * L2E_HI;
+  float r = fmaf(x, L2E_HI, -t);
+  r = fmaf(x, L2E_LO, r);
+  const float e = __builtin_amdgcn_exp2f(t);
+  return fmaf(e, r * 0.693147182464599609375f, e);
+}
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
@@ -336,6 +347,13 @@ int rotary_attention_launch(const float* qkv, float* o, const float* cos_tab, co
 // the same forward in bf16x3 arithmetic (attention_x3.hip)
 int rotary_attention_x3_launch(const float* qkv, float* o, const float* cos_tab, const float* sin_tab, int N, int T, int heads,
                                int hd, int rot_half, hipStream_t s, float* lse = nullptr, int out_split = 0);
+// streaming (flash-style) forward for sequences whose K and V do not fit the LDS (attention_stream.hip): hd 72 at T > 256, hd 64 at
+// T > 288, up to ATTN_STREAM_MAX_T tokens; x3 = 0 exact fp32 products, 1 bf16x3.  attn_stream_wanted: the two launchers above hand
+// (T, hd) over to it (and every shape while rgm_set_attn_stream(1) holds).
+constexpr int ATTN_STREAM_MAX_T = 8192;
+bool attn_stream_wanted(int T, int hd);
+int rotary_attention_stream_launch(const float* qkv, float* o, const float* cos_tab, const float* sin_tab, int N, int T, int heads, int hd,
+                                   int rot_half, hipStream_t s, float* lse, int out_split, int x3);
 // forward attention by mode: fp32 MFMA in fp32 mode, bf16x3 otherwise (rgm_set_gemm_precision); lse (optional) for the backward
 int rotary_attention_fwd(const float* qkv, float* o, const float* cos_tab, const float* sin_tab, int N, int T, int heads, int hd,
                          int rot_half, hipStream_t s, int out_split = 0, float* lse = nullptr);

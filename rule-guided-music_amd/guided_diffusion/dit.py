@@ -61,6 +61,22 @@ def _attach(root, dotted, param):
     mod.register_parameter(leaf, param)
 
 
+# Token counts the attention BACKWARD covers (csrc/attention_bwd.hip: K / V of a head in LDS), by head_dim.  The forward streams K and V
+# and runs up to 8192 tokens; everything that differentiates through a network (classifier guidance, DPS, guided editing) stays here.
+BACKWARD_MAX_TOKENS = {72: 256, 64: 288}
+
+
+def require_backward_tokens(n_tokens, head_dim, what):
+    """NotImplementedError (before any launch) when `what` would need the attention backward beyond its range."""
+    limit = BACKWARD_MAX_TOKENS.get(head_dim, 256)
+    if n_tokens > limit:
+        raise NotImplementedError(
+            f"{what} differentiates through the network, and the attention backward supports at most {limit} tokens at head_dim "
+            f"{head_dim} (a latent of height {limit // 2} at patch 8); this input has {n_tokens} tokens.  Unguided sampling, "
+            "classifier-free guidance and SCG run at any length up to 8192 tokens; for guided long excerpts use DiffCollage "
+            "(diff_collage/, overlapping 128-wide windows).")
+
+
 class _NativeDiT(nn.Module):
     """Parameter container + native handle shared by the eps-network and the classifiers."""
 
@@ -132,8 +148,11 @@ class _NativeDiT(nn.Module):
             _rgm.lib.rgm_dit_destroy(self._handle)
             self._handle = None
         if self._handle is None:
-            self._max_tokens = max(n_tokens, 2 * self.input_size[0] * self.input_size[1] // self.patch_size // 2 + 1, 257)
-            self._max_tokens = min(self._max_tokens, 288)
+            if n_tokens <= 288:
+                self._max_tokens = max(n_tokens, 2 * self.input_size[0] * self.input_size[1] // self.patch_size // 2 + 1, 257)
+                self._max_tokens = min(self._max_tokens, 288)
+            else:                         # long excerpts: the streaming attention forward, sized for the request
+                self._max_tokens = n_tokens
             cfg = DitCfg(depth=self.depth, hidden=self.hidden_size, heads=self.num_heads, patch=self.patch_size,
                          in_ch=self.in_channels, out_ch=self._out_ch, width=self.input_size[1],
                          n_embed=self._n_embed, kind=self._kind, n_out=self._n_out, max_tokens=self._max_tokens)
@@ -267,6 +286,7 @@ class DiTRotary(_NativeDiT):
         _rgm.require_cuda(x, t, y)
         N, _, H, W = x.shape
         assert W == self.input_size[1]
+        require_backward_tokens(H * W // self.patch_size, self.hidden_size // self.num_heads, "the eps-network's input gradient (DPS)")
         self._ensure_native(H * W // self.patch_size)
         x = x.detach().to(torch.float32).contiguous()
         t = self._as_index(t, torch.int64)
@@ -336,6 +356,7 @@ class DiTRotaryClassifier(_NativeDiT):
         loss_kind "xent": log p = log softmax(logits)[target], target (N,) integer"""
         _rgm.require_cuda(x, t, target)
         N, _, H, W = x.shape
+        require_backward_tokens(H * W // self.patch_size + 1, self.hidden_size // self.num_heads, "classifier guidance")
         self._ensure_native(H * W // self.patch_size + 1)
         x = x.detach().to(torch.float32).contiguous()
         t = self._as_index(t, torch.int64)

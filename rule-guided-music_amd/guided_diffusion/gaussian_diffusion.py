@@ -560,6 +560,19 @@ class GaussianDiffusion:
             grad = self._edit_grad(cond_fn, x, self._scale_timesteps(t), model_kwargs or {}, edit_kwargs)
         return p_mean_var["mean"].float() + p_mean_var["variance"] * grad.float()
 
+    @staticmethod
+    def _dps_length_check(model, x):
+        """DPS differentiates through the eps-network: a latent longer than the attention backward covers is refused before the
+        step's first launch (NotImplementedError naming the limit), not deep inside the VJP."""
+        import functools
+        from . import condition_functions as cf
+        from .dit import require_backward_tokens
+        inner = model.model if hasattr(model, "map_ts") else model
+        if isinstance(inner, functools.partial) and inner.func is cf.model_fn:
+            net = inner.keywords.get("model")
+            if hasattr(net, "patch_size") and x.dim() == 4:
+                require_backward_tokens(x.shape[2] * x.shape[3] // net.patch_size, net.hidden_size // net.num_heads, "DPS guidance")
+
     def _dps_mean(self, cond_fn, p_mean_var, x, t, model_kwargs, guidance_kwargs, model, embed_model, scale_factor=1.,
                   edit_kwargs=None):
         """DPS (reference :415-465): mean + step_size * d log p(rule | x0_hat(x_t)) / d x_t / sqrt(-log p), where
@@ -865,6 +878,8 @@ class GaussianDiffusion:
         # with scg_kwargs given the guidance schedule only gates the SCG search: condition_mean runs on every step (reference :691)
         guided = cond_fn is not None and (use_guidance or scg_kwargs is not None)
         dps = guided and getattr(guidance_kwargs, "method", None) == "dps"
+        if dps:
+            self._dps_length_check(model, x)
         search = scg_kwargs is not None and use_guidance and not dps and self._t0(t) > self.t_end
         if search:      # the two per-sample forwards before the candidate search: rows shared out over the ranks when there are any
             eps, grad = self._search_step_inputs(model, cond_fn if guided else None, x, t, model_kwargs, denoised_fn, edit_kwargs,

@@ -136,6 +136,22 @@ def targets_from_npz(path, target_rules, batch_size, device):
     return out
 
 
+def check_target_lengths(rules, frames, device):
+    """Every length-dependent rule target must have the length that rule has on the rolls this run makes (`frames` time steps,
+    8 per latent row: --image_size H 16 gives 8H).  note_density has 2 values per 128 frames, so the shipped YAML lists (made for
+    1024 frames) do not fit a longer excerpt: refused here with both lengths named, not deep inside the loss."""
+    probe = th.full((1, 3, 128, frames), -1.0, device=device)
+    for name, target in rules.items():
+        if "chord" in name or name not in midi_util.FUNC_DICT:
+            continue
+        with th.no_grad():
+            n = int(midi_util.FUNC_DICT[name](probe).shape[-1])
+        k = int(target.shape[-1])
+        if k != n:
+            raise ValueError(f"rule '{name}': the target has {k} values, which fits a roll of {frames * k // max(n, 1)} frames, but this "
+                             f"run makes rolls of {frames} frames (--image_size {frames // 8} 16), where '{name}' has {n} values")
+
+
 def output_dir_for(config_path, class_label):
     """cond_demo/<config path below cond_table/ or cond_demo/>_cls_<label>   (reference :42-46)."""
     root = "cond_demo/"
@@ -277,6 +293,7 @@ def main(argv=None):
         model_kwargs = {"rule": targets_from_npz(args.targets_npz, target_rules, args.batch_size, device)}
     else:
         model_kwargs = {"rule": build_target_rules(target_rules, args.batch_size, device)}
+    check_target_lengths(model_kwargs["rule"], 8 * gen_shape[2], device)
     classes = None
     if args.class_cond:
         classes = th.ones(size=(args.batch_size,), device=device, dtype=th.int) * args.class_label

@@ -21,6 +21,7 @@ import math
 import numpy as np
 
 F32 = np.float32
+SCORE_ELEMS = 1 << 26     # attention: beyond this many scores (256 MB) the score matrices are built one (sample, head) at a time
 
 
 def linear(x, w, b=None):
@@ -113,6 +114,18 @@ def attention(m, sd, pre, heads, cos, sin, cache=None):
     qkv = linear(m, sd[pre + "qkv.weight"], sd[pre + "qkv.bias"]).reshape(n, T, 3, heads, hd)
     q, k, v = (qkv[:, :, i].transpose(0, 2, 1, 3) for i in range(3))       # (n,heads,T,hd)
     q, k = apply_rotary(q, cos, sin), apply_rotary(k, cos, sin)
+    if cache is None and n * heads * T * T > SCORE_ELEMS:
+        # long excerpts: one (sample, head) score matrix at a time (the whole tensor is 4 GB at T = 8192, 16 heads)
+        o = np.empty((n, heads, T, hd), dtype=F32)
+        for i in range(n):
+            for h in range(heads):
+                s = (q[i, h] @ k[i, h].T) * F32(hd ** -0.5)
+                s = s - s.max(-1, keepdims=True)
+                p = np.exp(s)
+                p = (p / p.sum(-1, keepdims=True)).astype(F32)
+                o[i, h] = p @ v[i, h]
+        o = o.transpose(0, 2, 1, 3).reshape(n, T, D)
+        return linear(o, sd[pre + "proj.weight"], sd[pre + "proj.bias"])
     s = (q @ k.transpose(0, 1, 3, 2)) * F32(hd ** -0.5)
     s = s - s.max(-1, keepdims=True)
     p = np.exp(s)

@@ -61,11 +61,15 @@ struct StreamGeom {
   static_assert(X3 || (KROW / 16) % 2 == 1, "K slot stride must be odd");
 };
 
-template <int HD, int X3>
+// TAIL = 1: the last, partial query tile of every (sample, head), launched on its own (qb = qb0): there ALL eight waves run every
+// block, a wave without a query (q0 >= T) on the clamped query qc, storing nothing.  When such waves skipped the block's products,
+// the other waves of that workgroup returned wrong rows that differed from launch to launch (hd 64 bf16x3, T = 6001: 37 of 40
+// launches; hd 72: 1 of 40); running them gave 0 of 40.  The full tiles keep the TAIL = 0 instance, whose waves all have queries.
+template <int HD, int X3, int TAIL>
 __global__ __launch_bounds__(512) void rotary_attention_stream_kernel(const float* __restrict__ qkv, float* __restrict__ o,
                                                                       const float* __restrict__ cos_tab, const float* __restrict__ sin_tab,
                                                                       int T, int heads, int rot_half, float* __restrict__ lse, int out_split,
-                                                                      int qblocks) {
+                                                                      int qblocks, int qb0) {
   using G = StreamGeom<HD, X3>;
   constexpr int KP = G::KP, KROW = G::KROW, VROW = G::VROW, VBYTES = G::VBYTES, BUF = G::BUF;
   constexpr int KS = (HD + 15) / 16;        // x3: k16 steps of QK^T
@@ -83,7 +87,7 @@ __global__ __launch_bounds__(512) void rotary_attention_stream_kernel(const floa
   typedef split_t bf16x4 __attribute__((ext_vector_type(4)));
   extern __shared__ __attribute__((aligned(16))) char smem_s[];
 
-  const int pair = blockIdx.x / qblocks, qb = blockIdx.x - pair * qblocks;
+  const int pair = blockIdx.x / qblocks, qb = TAIL ? qb0 : blockIdx.x - pair * qblocks;
   const int n = pair / heads, head = pair - n * heads;
   const int D = heads * HD, D3 = 3 * D;
   const float* base = qkv + (long long)n * T * D3 + head * HD;
@@ -92,7 +96,7 @@ __global__ __launch_bounds__(512) void rotary_attention_stream_kernel(const floa
   const int R = 2 * rot_half;
   const int nb = (T + SKB - 1) / SKB;
   const int q0 = qb * SQ + wave * 32;
-  const bool active = q0 < T;                                  // wave-uniform: this wave has queries
+  const bool active = TAIL || q0 < T;                          // wave-uniform: this wave runs the blocks (see TAIL)
   const int q = q0 + l31;
   const int qc = min(q, T - 1);
 
@@ -362,7 +366,7 @@ __global__ __launch_bounds__(512) void rotary_attention_stream_kernel(const floa
     }
   }
 
-  if (!active || q >= T) return;
+  if (!active || q >= T) return;   // (q >= T covers the waves TAIL runs without queries)
   const float inv = 1.0f / l_run;
   if (lse && hh == 0)   // natural-log sum-exp of the scaled scores, saved for the backward
     lse[((long long)n * heads + head) * T + q] = X3 ? (m_run + log2f(l_run)) * 0.693147180559945309417f : m_run + logf(l_run);
@@ -388,17 +392,26 @@ __global__ __launch_bounds__(512) void rotary_attention_stream_kernel(const floa
     }
 }
 
-template <int HD, int X3>
-static int launch_stream(const float* qkv, float* o, const float* ct, const float* st, int N, int T, int heads, int rot_half, float* lse,
-                         int out_split, hipStream_t s) {
+template <int HD, int X3, int TAIL>
+static int launch_stream_part(const float* qkv, float* o, const float* ct, const float* st, int N, int T, int heads, int rot_half, float* lse,
+                              int out_split, int qblocks, int qb0, hipStream_t s) {
   const size_t lds = attn_lds_one_per_cu(2 * (size_t)StreamGeom<HD, X3>::BUF);   // two block buffers; one workgroup per CU
-  auto kern = rotary_attention_stream_kernel<HD, X3>;
+  auto kern = rotary_attention_stream_kernel<HD, X3, TAIL>;
   static bool prepared = false;
   if (!prepared) RGM_TRY(attn_prepare_kernel(kern, 512, lds, "rotary_attention_stream_kernel"));
   prepared = true;
-  const int qblocks = (T + SQ - 1) / SQ;
-  hipLaunchKernelGGL(kern, dim3(N * heads * qblocks), dim3(512), lds, s, qkv, o, ct, st, T, heads, rot_half, lse, out_split, qblocks);
+  hipLaunchKernelGGL(kern, dim3(N * heads * qblocks), dim3(512), lds, s, qkv, o, ct, st, T, heads, rot_half, lse, out_split, qblocks, qb0);
   RGM_LAUNCH_CHECK();
+  return RGM_OK;
+}
+
+// the full query tiles, then (T % 256 != 0) the partial last tile of every (sample, head) with the TAIL instance
+template <int HD, int X3>
+static int launch_stream(const float* qkv, float* o, const float* ct, const float* st, int N, int T, int heads, int rot_half, float* lse,
+                         int out_split, hipStream_t s) {
+  const int full = T / SQ;
+  if (full > 0) RGM_TRY((launch_stream_part<HD, X3, 0>(qkv, o, ct, st, N, T, heads, rot_half, lse, out_split, full, 0, s)));
+  if (T % SQ) RGM_TRY((launch_stream_part<HD, X3, 1>(qkv, o, ct, st, N, T, heads, rot_half, lse, out_split, 1, full, s)));
   return RGM_OK;
 }
 

@@ -7,6 +7,9 @@ the teacher-forced noise queue) it reuses:  `python tests/golden/make_golden_lon
     long_dit_xl2.npz    XL-2 eps-network forward at H = 136 (B 2), 256 (B 2), 512 (B 1): T = 272, 512, 1024 tokens
     long_dit_xl28.npz   XL-28 forward at H = 256, B = 2
     long_ddim.npz       one teacher-forced DDIM step (ddim50 chain, eta = 1, injected noise) at H = 256, B = 2, XL-2
+    long_dit_xl2_edge.npz  XL-2 forward at H = 1040 (B 2; T = 2080: partial last query tile and key block) and H = 4096 (B 1;
+                        T = 8192, the streaming kernel's ceiling).  x is NOT stored: x{H} = RandomState(x{H}_seed).randn(B, 4, H, 16);
+                        t{H}, y{H} are, with the reference output at the latent rows rows{H} = edge_rows(H) only (out{H}: (B, 4, R, 16))
 
 Seeds are pinned by name in LONG_SEEDS and stored as ONE-ELEMENT arrays (make_golden.py's FIXTURE_SEEDS check reads 0-d `*seed`
 arrays only); tests/test_long_fixtures.py holds the fixtures to this table."""
@@ -25,7 +28,9 @@ LONG_SEEDS = {
     "long_dit_xl2": {"seed": 1, "x_seed": 700},
     "long_dit_xl28": {"seed": 1, "x_seed": 701},
     "long_ddim": {"seed": 11, "x_seed": 702},
+    "long_dit_xl2_edge": {"seed": 1, "x1040_seed": 704, "x4096_seed": 705},
 }
+EDGE_SHAPES = ((1040, 2), (4096, 1))      # (H, B) of long_dit_xl2_edge
 LIMIT = 1024 * 1024
 
 
@@ -60,6 +65,34 @@ def g_forward(name, arch, shapes):
     save(name, **seeds(name), **out)
 
 
+def edge_rows(H):
+    """latent rows stored of an H-row output: the first and last 64, every 16th in between"""
+    return np.unique(np.concatenate((np.arange(64), np.arange(64, H - 64, 16), np.arange(H - 64, H))))
+
+
+def edge_input(name, H, B):
+    return np.random.RandomState(LONG_SEEDS[name][f"x{H}_seed"]).randn(B, 4, H, 16).astype(F32)
+
+
+def g_edge():
+    name = "long_dit_xl2_edge"
+    print(f"[{name}]")
+    m, sd = mg.ref_dit(mg.XL2, LONG_SEEDS[name]["seed"])
+    out = {}
+    for H, B in EDGE_SHAPES:
+        x = edge_input(name, H, B)
+        t = np.array([917, 3][:B], dtype=np.int64)
+        y = np.array([2, 3][:B], dtype=np.int64)                      # 3 == the null label
+        with torch.no_grad():
+            ref = m(torch.from_numpy(x), torch.from_numpy(t), torch.from_numpy(y)).numpy()
+        rows = edge_rows(H)
+        ora = mg.odit.dit_forward(sd, x, t, y, depth=2, heads=16)
+        mg.err(f"forward H={H} (T={2 * H})", ora, ref)
+        out.update({f"t{H}": t, f"y{H}": y, f"rows{H}": rows.astype(np.int64), f"out{H}": np.ascontiguousarray(ref[:, :, rows])})
+        del ref, ora
+    save(name, **seeds(name), **out)
+
+
 def g_ddim():
     name = "long_ddim"
     print(f"[{name}]")
@@ -83,7 +116,7 @@ def g_ddim():
 
 
 if __name__ == "__main__":
-    which = set(sys.argv[1:]) or {"xl2", "xl28", "ddim"}
+    which = set(sys.argv[1:]) or {"xl2", "xl28", "ddim", "edge"}
     torch.set_num_threads(8)
     if "xl2" in which:
         g_forward("long_dit_xl2", mg.XL2, [(136, 2), (256, 2), (512, 1)])
@@ -91,3 +124,5 @@ if __name__ == "__main__":
         g_forward("long_dit_xl28", mg.XL28, [(256, 2)])
     if "ddim" in which:
         g_ddim()
+    if "edge" in which:
+        g_edge()

@@ -45,3 +45,17 @@ def test_oracle_matches_long_reference_forward(H):
     out = odit.dit_forward(sd, x, t, y, depth=2, heads=16)
     assert out.shape == x.shape
     assert rel_err(out, g[f"out{H}"]) < 1e-4
+
+
+@pytest.mark.parametrize("H", [1040, 4096])
+def test_oracle_matches_long_reference_forward_at_the_edges(H):
+    """the numpy oracle reproduces the reference at T = 2080 (partial last query tile and key block of the streaming kernel) and at
+    its ceiling T = 8192: the stored slices (the first and last 64 latent rows, every 16th between) of an input rebuilt from its seed"""
+    g = load_golden("long_dit_xl2_edge")
+    sd = synth.dit_state_dict(int(g["seed"][0]), **XL2)
+    t, y, rows = g[f"t{H}"], g[f"y{H}"], g[f"rows{H}"]
+    x = np.random.RandomState(int(g[f"x{H}_seed"][0])).randn(len(t), 4, H, 16).astype(np.float32)
+    assert rows[0] == 0 and rows[-1] == H - 1 and np.array_equal(rows[:64], np.arange(64))
+    out = odit.dit_forward(sd, x, t, y, depth=2, heads=16)
+    assert out.shape == x.shape
+    assert rel_err(out[:, :, rows], g[f"out{H}"]) < 1e-4

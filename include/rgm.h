@@ -230,6 +230,31 @@ int rgm_ddpm_step_learned_g(const float* x, const float* eps, const float* var_v
 int rgm_ddim_step(const float* x, const float* eps, const float* grad, const float* noise, const int64_t* t,
                   const float* const* tables_host, int clip_denoised, int t_end, float eta, float* sample,
                   float* pred_xstart, float* g_out, int N, int E, void* stream);
+/* ddim_reverse_sample (:978-1014), the DDIM ODE towards noise (eta = 0): x0 = c1 x - c2 eps (clip); eps' = (c1 x - x0) / c2 (re-derived,
+ * so a clip shows in it); sample = sqrt(abar_next) x0 + sqrt(1 - abar_next) eps', abar_next = alphas_cumprod[t + 1], 0 at the last index
+ * t == num_timesteps - 1 (the chain length = the tables' length).  Evaluated in fp64 per element, stored as fp32. */
+int rgm_ddim_reverse_step(const float* x, const float* eps, const int64_t* t, const float* const* tables_host, int num_timesteps,
+                          int clip_denoised, float* sample, float* pred_xstart, int N, int E, void* stream);
+/* _vb_terms_bpd (:1145-1178) and the two per-step errors of calc_bpd_loop (:1311-1314) in one pass.  Per sample b:
+ *   vb[b]         t[b] > 0: mean of normal_kl(q_posterior_mean(x_start, x_t), post_logvar_tab[t], model_mean, model_log_variance);
+ *                 t[b] == 0: mean of -discretized_gaussian_log_likelihood(x_start, model_mean, 0.5 model_log_variance); both / ln 2
+ *   xstart_mse[b] mean((pred_xstart - x_start)^2)                                   (may be NULL)
+ *   eps_mse[b]    mean(((c1 x_t - pred_xstart) / c2 - noise)^2), needs noise         (both may be NULL)
+ *   pred_xstart   (N,E) or NULL: c1 x_t - c2 eps, clipped to [-1, 1] if asked.
+ * Variances: tables_host[5] (fixed), or var_values (N,E) with min_log_tab / max_log_tab exactly as rgm_ddpm_step_learned takes them.
+ * post_logvar_tab: device float32 posterior_log_variance_clipped.  model_mean (N,E) or NULL: the network's own mean (PREVIOUS_X)
+ * instead of the posterior mean of pred_xstart; model_xstart (N,E) or NULL: the x0 estimate itself instead of c1 x_t - c2 eps (eps may
+ * then be NULL).  partials: device scratch of rgm_vb_terms_partials(N, E) doubles.  fp64 per element; fixed partition of E into
+ * chunks of 2048 and a fixed combination order, no atomics: bitwise repeatable, and a sample's outputs do not depend on N or its row. */
+int64_t rgm_vb_terms_partials(int N, int E);
+int rgm_vb_terms(const float* x_start, const float* x_t, const float* eps, const float* noise, const int64_t* t,
+                 const float* const* tables_host, const float* post_logvar_tab, const float* var_values, const float* min_log_tab,
+                 const float* max_log_tab, const float* model_mean, const float* model_xstart, int clip_denoised, double* partials,
+                 float* vb, float* xstart_mse, float* eps_mse, float* pred_xstart, int N, int E, void* stream);
+/* _prior_bpd (:1255-1272): out[b] = mean(normal_kl(sqrt_alphas_cumprod[T-1] x_start, log_one_minus_alphas_cumprod[T-1], 0, 0)) / ln 2;
+ * the two table entries as float32 values; the same reduction (partials: rgm_vb_terms_partials(N, E) doubles suffice). */
+int rgm_prior_bpd(const float* x_start, float sqrt_alphas_cumprod_T, float log_one_minus_alphas_cumprod_T, double* partials, float* out,
+                  int N, int E, void* stream);
 /* scg_sample candidate expansion (:509-514): cand[k][b] = mean[b] + g[b] * noise[k][b], k < n. */
 int rgm_scg_candidates(const float* mean, const float* g, const float* noise, float* cand, int n, int B, int E,
                        void* stream);

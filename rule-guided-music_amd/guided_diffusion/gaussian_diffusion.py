@@ -25,6 +25,10 @@ All three mean types (EPSILON, START_X, PREVIOUS_X) and fixed / learned variance
 the mean afterwards, _prevx_fix); SCG on a learn_sigma=True network uses the per-element noise scale.  Not implemented: DPS on a
 learn_sigma=True network (raises -- the reference asserts there too, :421) and the training losses.
 SCG / DPS score candidates with an eps-predicting network (as every shipped configuration does).
+
+What takes an existing latent as its input runs on forwards of the frozen network alone, at every length the forward serves:
+ddim_reverse_sample / ddim_reverse_sample_loop (DDIM inversion, rgm_ddim_reverse_step) and _vb_terms_bpd, _prior_bpd, calc_bpd_loop
+(the variational bound in bits per dimension with the per-timestep x0 / eps errors: rgm_vb_terms, a deterministic two-stage reduction).
 """
 import ctypes as C
 import enum
@@ -188,6 +192,7 @@ class GaussianDiffusion:
             assert out.shape[1] == 2 * C_, f"learned variances need a 2C-channel model output, got {tuple(out.shape)}"
             out, self._var_values = out[:, :C_].contiguous(), out[:, C_:].float().contiguous()
         self._prevx = None
+        self._x0_direct = None      # the x0 estimate itself where it does not come from eps (START_X, denoised_fn): _vb_terms reads it
         if self.model_mean_type == ModelMeanType.PREVIOUS_X:
             # the network predicts x_{t-1} (reference :331-338): pred_xstart = process_xstart(_predict_xstart_from_xprev) (:374-384) while
             # the MEAN stays the raw output whatever denoised_fn / clip_denoised do to x0 -- _step restores it after the fused kernel
@@ -205,6 +210,7 @@ class GaussianDiffusion:
         x0 = out.float() if start_x else self._predict_xstart_from_eps(x, t, out)
         if denoised_fn is not None:
             x0 = denoised_fn(x0)
+        self._x0_direct = x0.float().contiguous()
         ones = th.ones((1,) * x.dim(), dtype=th.float32, device=x.device)
         return self._edit_eps(x, th.zeros_like(x, dtype=th.float32), t, False, {"gt": x0, "mask": ones})
 
@@ -1074,6 +1080,152 @@ class GaussianDiffusion:
                 scg_kwargs=scg_kwargs, edit_kwargs=edit_kwargs, record=record):
             pass
         return final["sample"]
+
+    # ------------------------------------------------------------------ inversion and evaluation (a FROZEN network: forwards only)
+    def _predict_xstart_from_xprev(self, x_t, t, xprev):
+        assert x_t.shape == xprev.shape
+        return (self._per_sample(1.0 / self.posterior_mean_coef1, t, x_t) * xprev
+                - self._per_sample(self.posterior_mean_coef2 / self.posterior_mean_coef1, t, x_t) * x_t)
+
+    def _frozen_eps(self, model, x, t, denoised_fn, model_kwargs):
+        """The eps estimate of the (re-spaced) frozen network at (x, t), as the sampling steps obtain it."""
+        with th.no_grad():
+            return self._model_eps(x, self._eps_net(self._wrap_model(model), x, t, **(model_kwargs or {})), t, denoised_fn)
+
+    def _ddim_reverse_step(self, x, eps, t, clip_denoised):
+        """One rgm_ddim_reverse_step launch -> (sample, pred_xstart)."""
+        _rgm.require_cuda(x, eps, t)
+        x, eps = x.float().contiguous(), eps.float().contiguous()
+        assert eps.shape == x.shape, f"model output {tuple(eps.shape)} vs x {tuple(x.shape)}"
+        tt = t.long().contiguous()
+        N = x.shape[0]
+        assert tt.shape == (N,)
+        sample, x0 = th.empty_like(x), th.empty_like(x)
+        with th.cuda.device(x.device):
+            _rgm.check(_rgm.lib.rgm_ddim_reverse_step(_rgm.ptr(x), _rgm.ptr(eps), _rgm.ptr(tt), self._tab(x.device).ptrs,
+                                                      self.num_timesteps, int(bool(clip_denoised)), _rgm.ptr(sample), _rgm.ptr(x0),
+                                                      N, x.numel() // N, _rgm.current_stream()))
+        return sample, x0
+
+    def ddim_reverse_sample(self, model, x, t, clip_denoised=True, denoised_fn=None, model_kwargs=None, eta=0.0):
+        """x_{t+1} from x_t along the DDIM ODE (reference :978-1014) -> {'sample', 'pred_xstart'}.  Not batch-sharded."""
+        assert eta == 0.0, "Reverse ODE only for deterministic path"
+        eps = self._frozen_eps(model, x, t, denoised_fn, model_kwargs)
+        sample, x0 = self._ddim_reverse_step(x, eps, t, clip_denoised)
+        if getattr(self, "_prevx", None) is not None:      # PREVIOUS_X: x0 straight from the network's x_{t-1} (see _prevx_fix)
+            x0 = self._prevx_x0.clamp(-1, 1) if clip_denoised else self._prevx_x0
+        return {"sample": sample, "pred_xstart": x0}
+
+    def ddim_reverse_sample_loop(self, model, x_start, num_steps=None, clip_denoised=True, denoised_fn=None, model_kwargs=None,
+                                 progress=False):
+        """DDIM inversion: the reverse step at chain indices 0, 1, ..., num_steps - 2 -> the latent at index num_steps - 1 (default:
+        the whole chain), i.e. the start `noise=` of a sampling loop under edit_kwargs['noise_level'] == num_steps.  The chain ASCENDS,
+        so the conditioning computed ahead (which assumes a descending chain) stays off: _t_host is left unset and every forward runs
+        its own adaLN pass -- the loop is the same launches as ddim_reverse_sample called by hand."""
+        num_steps = self.num_timesteps if num_steps is None else int(num_steps)
+        assert 1 <= num_steps <= self.num_timesteps, f"num_steps {num_steps} outside 1 .. {self.num_timesteps}"
+        indices = range(num_steps - 1)
+        if progress:
+            from tqdm.auto import tqdm
+            indices = tqdm(indices)
+        img = x_start.float()
+        for i in indices:
+            t = th.full((img.shape[0],), i, dtype=th.int64, device=img.device)
+            img = self.ddim_reverse_sample(model, img, t, clip_denoised=clip_denoised, denoised_fn=denoised_fn,
+                                           model_kwargs=model_kwargs)["sample"]
+        return img
+
+    def _partials(self, N, E, device):
+        n = int(_rgm.lib.rgm_vb_terms_partials(N, E))
+        return th.empty(n, dtype=th.float64, device=device)
+
+    def _vb_terms(self, x_start, x_t, eps, noise, t, clip_denoised, want_mse=True):
+        """One rgm_vb_terms launch on an eps estimate (what _model_eps returned, whose side results -- learned variances, a PREVIOUS_X
+        network's own mean -- it picks up) -> (vb, xstart_mse or None, eps_mse or None, pred_xstart)."""
+        _rgm.require_cuda(x_start, x_t, eps, noise, t)
+        x_start, x_t, eps = x_start.float().contiguous(), x_t.float().contiguous(), eps.float().contiguous()
+        assert x_start.shape == x_t.shape == eps.shape, (tuple(x_start.shape), tuple(x_t.shape), tuple(eps.shape))
+        noise = None if noise is None else noise.float().contiguous()
+        assert noise is None or noise.shape == x_t.shape
+        tt = t.long().contiguous()
+        N = x_t.shape[0]
+        assert tt.shape == (N,)
+        E = x_t.numel() // N
+        dev = x_t.device
+        vv = lo = hi = None
+        if self._learned():
+            vv = self._var_values
+            assert vv is not None and vv.shape == x_t.shape
+            if self.model_var_type == ModelVarType.LEARNED_RANGE:
+                lt = self._learned_tabs(dev)
+                lo, hi = lt[0], lt[1]
+        prevx = getattr(self, "_prevx", None)
+        mean = xs = None
+        if prevx is not None:
+            assert prevx.shape == x_t.shape
+            mean, xs = prevx, self._prevx_x0.contiguous()
+        elif getattr(self, "_x0_direct", None) is not None:
+            # START_X: the network's x0 itself -- the eps round trip of the sampling steps costs c2 * 6e-8 of it at large t
+            xs = self._x0_direct
+            assert xs.shape == x_t.shape
+        vb = th.empty(N, dtype=th.float32, device=dev)
+        xm = th.empty(N, dtype=th.float32, device=dev) if want_mse else None
+        em = th.empty(N, dtype=th.float32, device=dev) if (want_mse and noise is not None) else None
+        x0 = th.empty_like(x_t)
+        part = self._partials(N, E, dev)
+        with th.cuda.device(dev):
+            _rgm.check(_rgm.lib.rgm_vb_terms(_rgm.ptr(x_start), _rgm.ptr(x_t), _rgm.ptr(eps), _rgm.ptr(noise), _rgm.ptr(tt),
+                                             self._tab(dev).ptrs, _rgm.ptr(self._learned_tabs(dev)[0]), _rgm.ptr(vv), _rgm.ptr(lo),
+                                             _rgm.ptr(hi), _rgm.ptr(mean), _rgm.ptr(xs), int(bool(clip_denoised)), _rgm.ptr(part),
+                                             _rgm.ptr(vb), _rgm.ptr(xm), _rgm.ptr(em), _rgm.ptr(x0), N, E, _rgm.current_stream()))
+        return vb, xm, em, x0
+
+    def _vb_terms_bpd(self, model, x_start, x_t, t, clip_denoised=True, model_kwargs=None):
+        """A term of the variational bound in bits per dimension (reference :1145-1178) -> {'output' (N,), 'pred_xstart'}: the
+        decoder NLL where t == 0, KL(q(x_{t-1} | x_t, x_0) || p(x_{t-1} | x_t)) elsewhere.  Not batch-sharded."""
+        eps = self._frozen_eps(model, x_t, t, None, model_kwargs)
+        vb, _, _, x0 = self._vb_terms(x_start, x_t, eps, None, t, clip_denoised, want_mse=False)
+        return {"output": vb, "pred_xstart": x0}
+
+    def _prior_bpd(self, x_start):
+        """The prior term KL(q(x_T | x_0) || N(0, I)) in bits per dimension (reference :1255-1272) -> (N,)."""
+        _rgm.require_cuda(x_start)
+        x_start = x_start.float().contiguous()
+        N = x_start.shape[0]
+        E = x_start.numel() // N
+        out = th.empty(N, dtype=th.float32, device=x_start.device)
+        part = self._partials(N, E, x_start.device)
+        with th.cuda.device(x_start.device):
+            _rgm.check(_rgm.lib.rgm_prior_bpd(_rgm.ptr(x_start), float(np.float32(self.sqrt_alphas_cumprod[-1])),
+                                              float(np.float32(self.log_one_minus_alphas_cumprod[-1])), _rgm.ptr(part), _rgm.ptr(out),
+                                              N, E, _rgm.current_stream()))
+        return out
+
+    def calc_bpd_loop(self, model, x_start, clip_denoised=True, model_kwargs=None):
+        """The whole variational bound in bits per dimension and the per-timestep errors (reference :1274-1328) ->
+        {'total_bpd' (N,), 'prior_bpd' (N,), 'vb', 'xstart_mse', 'mse' (N, T)}, columns in the reference's order: column 0 is the LAST
+        timestep.  One forward and one rgm_vb_terms launch per timestep; the noise of q_sample comes from _draw, one draw per step in
+        the loop's order.  The chain descends with every sample at the same index, so the loop sets _t_host like the sampling loops do
+        (conditioning computed ahead; same values as the per-forward pass).  Not batch-sharded: every rank computes the whole batch."""
+        x_start = x_start.float().contiguous()
+        B, dev = x_start.shape[0], x_start.device
+        vb, xstart_mse, mse = [], [], []
+        for i in range(self.num_timesteps)[::-1]:
+            t = th.full((B,), i, dtype=th.int64, device=dev)
+            noise = self._draw(x_start.shape, dev)
+            x_t = self.q_sample(x_start, t, noise=noise)
+            self._t_host = i
+            try:
+                eps = self._frozen_eps(model, x_t, t, None, model_kwargs)
+            finally:
+                self._t_host = None
+            v, xm, em, _ = self._vb_terms(x_start, x_t, eps, noise, t, clip_denoised)
+            vb.append(v)
+            xstart_mse.append(xm)
+            mse.append(em)
+        vb, xstart_mse, mse = th.stack(vb, dim=1), th.stack(xstart_mse, dim=1), th.stack(mse, dim=1)
+        prior_bpd = self._prior_bpd(x_start)
+        return {"total_bpd": vb.sum(dim=1) + prior_bpd, "prior_bpd": prior_bpd, "vb": vb, "xstart_mse": xstart_mse, "mse": mse}
 
     def training_losses(self, *a, **k):
         raise NotImplementedError("training is out of scope of the sampling hot path (SURVEY 2, row 12)")

@@ -111,6 +111,9 @@ def edit_target_rules(target_rules, gt_partial, batch_size, device):
     return out, orig
 
 
+LAST_START = None      # the start latent of the last run under --edit_start ddim_inversion (None: the loop drew its own)
+
+
 def main(argv=None):
     args = create_argparser().parse_args(argv)
     root = "edit_demo/"
@@ -125,6 +128,8 @@ def main(argv=None):
         args.dir += "_nochord"
     if substituted:
         args.dir += "_synthsrc"
+    if args.edit_start == "ddim_inversion":
+        args.dir += "_inv"
     logger.configure(args=args, comm=comm)
     if config.sampling.use_ddim:
         args.timestep_respacing = config.sampling.timestep_respacing
@@ -147,7 +152,8 @@ def main(argv=None):
     edit_kwargs["l_start_pix"], edit_kwargs["l_end_pix"] = edit_kwargs["l_start"] * 8, edit_kwargs["l_end"] * 8
     gt = load_source(edit_kwargs.get("source", "synthetic"), gen_shape[2] * 8, args.fs, device, allow_synthetic=args.allow_synthetic_source)
     if args.save_files and rank0:
-        _sr.write_run_metadata(save_dir, args, {"source": edit_kwargs.get("source", "synthetic"), "source_substituted_by_synthetic": bool(substituted)})
+        _sr.write_run_metadata(save_dir, args, {"source": edit_kwargs.get("source", "synthetic"), "source_substituted_by_synthetic": bool(substituted),
+                                                   "edit_start": args.edit_start})
     gt_latent = _encode(gt, embed_model, scale_factor=args.scale_factor)
     mask = th.ones_like(gt_latent)
     mask[:, :, edit_kwargs["l_start"]:edit_kwargs["l_end"], :] = 0.
@@ -161,6 +167,15 @@ def main(argv=None):
         model_kwargs["y"] = classes
     use_scg = bool(getattr(config.guidance, "scg", getattr(config.guidance, "beam", False)))
 
+    global LAST_START
+    start = None
+    if args.edit_start == "ddim_inversion":
+        # the chain starts from the DDIM inversion of the encoded source (deterministic: the part that is re-generated is remembered)
+        # instead of q_sample(source, noise_level): one pass up the chain, no guidance, then handed to the loop as its `noise`
+        start = diffusion.ddim_reverse_sample_loop(P.model_fn, gt_latent.expand(gen_shape).contiguous(), num_steps=int(edit_kwargs["noise_level"]),
+                                                   clip_denoised=args.clip_denoised, model_kwargs=model_kwargs, progress=args.progress)
+    LAST_START = start
+
     all_results = pd.DataFrame()
     count_samples = 0
     while count_samples < args.num_samples:
@@ -168,7 +183,7 @@ def main(argv=None):
             P.model_fn, gen_shape, clip_denoised=args.clip_denoised, model_kwargs=model_kwargs, device=device, cond_fn=P.cond_fn,
             embed_model=embed_model if config.guidance.vae else None, scale_factor=args.scale_factor,
             guidance_kwargs=config.guidance, scg_kwargs=vars(config.scg) if use_scg else None, edit_kwargs=edit_kwargs,
-            t_end=config.sampling.t_end, record=args.record, progress=args.progress)
+            t_end=config.sampling.t_end, record=args.record, progress=args.progress, **({} if start is None else {"noise": start}))
         sample = midi_util.decode_sample_for_midi(sample, embed_model=embed_model, scale_factor=args.scale_factor, threshold=-0.95)
         arr = sample.cpu().numpy().transpose(0, 3, 1, 2)
         arr_gt = ((gt + 1) * 63.5).clamp(0, 127).to(th.uint8).cpu().numpy()
@@ -201,6 +216,10 @@ def create_argparser():
     parser.add_argument("--allow_synthetic_source", default=False, type=lambda v: str(v).lower() in ("yes", "true", "t", "y", "1"),
                         help="edit.source 'dataset' needs the reference's data loader; True substitutes a seeded synthetic roll "
                              "(marked in the output directory name and run_metadata.json)")
+    parser.add_argument("--edit_start", default="noise", choices=["noise", "ddim_inversion"],
+                        help="where the chain starts: 'noise' = the source noised to edit.noise_level with fresh noise; 'ddim_inversion' = "
+                             "the DDIM inversion of the source up to that level (deterministic; costs noise_level - 1 extra forwards of the "
+                             "chain in use, so on a DDPM config as many as the edit itself; '_inv' in the output directory name)")
     return parser
 
 

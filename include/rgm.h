@@ -355,7 +355,9 @@ int rgm_row_loss(const float* a, const float* b, float* out, int rows, int K, in
  *   loss_kind 1 (kind-2 handle): log p = -sum_w CE(chord_logits[w], target[w]), target int64 (N, H/width)
  *                                                                                 [grad_nn_zt_chord, both=False]
  *   loss_kind 1 (kind-1 handle): log p = log softmax(logits)[target], target int64 (N,)             [grad_nn_zt_xentropy :46-56]
- * grad_x (N,in_ch,H,width) = d(sum log p)/dx * scale;  logits_out (N[,H/width], n_out) or NULL. */
+ * grad_x (N,in_ch,H,width) = d(sum log p)/dx * scale;  logits_out (N[,H/width], n_out) or NULL.
+ * Any H the handle's max_tokens allows (classifiers: H*width/patch + 1 tokens): beyond 256 (hd 72) / 288 (hd 64) tokens the attention
+ * backward streams (csrc/attention_bwd_stream.hip).  The workspace keeps every block's activations: 40 * hidden bytes per token and block. */
 size_t rgm_dit_grad_workspace_bytes(const rgm_dit* h, int N, int H);
 int rgm_dit_cls_value_and_grad(rgm_dit* h, const float* x, const int64_t* t, const void* target, int loss_kind,
                                float scale, float* logits_out, float* grad_x, int N, int H, void* ws,
@@ -366,16 +368,24 @@ int rgm_dit_cls_value_and_grad(rgm_dit* h, const float* x, const int64_t* t, con
  * rgm_dit_enable_grad(h) first: it keeps W^T copies of the eps-network's Linear weights (1.8 GB at XL); workspace =
  * rgm_dit_grad_workspace_bytes(h, N, H).  Two phases that may be separate calls on the same workspace: forward
  * (x, t [, y] given; g_eps/grad_x NULL) saves the activations and writes eps_out; backward (x NULL; g_eps, grad_x given)
- * consumes them -- DPS forms g_eps from the classifier's gradient at x0(eps) in between. */
+ * consumes them -- DPS forms g_eps from the classifier's gradient at x0(eps) in between.  Any H the handle's max_tokens allows. */
 int rgm_dit_enable_grad(rgm_dit* h);
 int rgm_dit_vjp(rgm_dit* h, const float* x, const int64_t* t, const int32_t* y, const float* g_eps, float* eps_out,
                 float* grad_x, int N, int H, void* ws, size_t ws_bytes, void* stream);
-/* d(qkv) of the RotaryAttention core from dO, the saved qkv, O and per-query log-sum-exp (N, heads, T); hd = 64. */
 /* Attention launches of the classifier path (DiTRotary-S/8-cls: 257 tokens = 9 tiles of 32 on 8 waves, 6 heads x the sampler's batch of
  * (sample, head) pairs on 256 CUs; ref guided_diffusion/dit.py:803-831 + condition_functions.py:58-64): -1 (default) = per-tile workgroups
  * (backward: one per query / key tile, partial sums through LDS in a fixed order; forward: two per (sample, head)) whenever the
  * (sample, head) grid would leave CUs idle, 0 = never, 1 = always.  Same values to the last bit of the summation order. */
 int rgm_set_attn_split(int mode);
+/* The streaming attention backward (csrc/attention_bwd_stream.hip) for EVERY sequence length of hd 64 / 72, not only where the resident
+ * kernels cannot hold a head: comparisons of the two on the same inputs, tests.  1 = on, 0 = off (default).  Returns the previous
+ * setting.  rgm_attn_bwd_stream_launches: how many backward launches took the streaming pair so far in this process. */
+int rgm_set_attn_bwd_stream(int on);
+long long rgm_attn_bwd_stream_launches(void);
+/* d(qkv) (N*T, 3*heads*hd) of the RotaryAttention core from dO, the saved qkv, O and per-query log-sum-exp (N, heads, T); hd in {64, 72},
+ * 1 <= T <= 8192.  Q / dO resp. K / V of a head stay in LDS up to T = 256 (hd 72) / 288 (hd 64) -- the resident kernels,
+ * csrc/attention_bwd.hip; longer sequences run the streaming (flash-style) pair, csrc/attention_bwd_stream.hip, in the same arithmetic:
+ * deterministic, no atomics. */
 int rgm_rotary_attention_bwd(const float* qkv, const float* o, const float* d_o, const float* lse, float* dqkv,
                              const float* cos_tab, const float* sin_tab, int N, int T, int heads, int hd,
                              int rot_half, void* stream);

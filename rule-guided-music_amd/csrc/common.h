@@ -361,6 +361,12 @@ int rotary_attention_fwd(const float* qkv, float* o, const float* cos_tab, const
 int rotary_attention_bwd_launch(const float* qkv, const float* o, const float* d_o, const float* lse, float* dqkv,
                                 const float* cos_tab, const float* sin_tab, int N, int T, int heads, int hd,
                                 int rot_half, hipStream_t s, int osplit = 0);   // osplit: d(qkv) as split rows (a pre-split dgrad GEMM reads them next)
+// streaming backward for the sequences the resident pair cannot hold (attention_bwd_stream.hip): hd 72 at T > 256, hd 64 at T > 288, up to
+// ATTN_STREAM_MAX_T tokens; rotary_attention_bwd_launch hands those over (and every shape while rgm_set_attn_bwd_stream(1) holds)
+bool attn_bwd_stream_wanted(int T, int hd);
+int rotary_attention_bwd_stream_launch(const float* qkv, const float* o, const float* d_o, const float* lse, float* dqkv,
+                                       const float* cos_tab, const float* sin_tab, int N, int T, int heads, int hd, int rot_half,
+                                       hipStream_t s, int osplit, int x3);
 int transpose_launch(const float* in, float* out, int R, int Cc, int out_ld, int batch, hipStream_t s);
 int attn_split_mode();   // rgm_set_attn_split (attention_bwd.hip): -1 auto, 0 never, 1 always
 constexpr int ATTN_SPLIT_MAX_PAIRS = 96;   // auto: per-tile attention workgroups up to this many (sample, head) pairs (B <= 16 for the 6-head classifiers)

@@ -156,7 +156,8 @@ extern "C" int rgm_dit_create(const rgm_dit_cfg* c, rgm_dit** out) {
   RGM_REQUIRE(hd == 64 || hd == 72, "dit_create: head_dim %d (64 or 72 supported)", hd);
   RGM_REQUIRE((c->in_ch * c->patch) % 32 == 0, "dit_create: in_ch*patch=%d must be a multiple of 32", c->in_ch * c->patch);
   RGM_REQUIRE(c->kind >= 0 && c->kind <= 2, "dit_create: kind %d", c->kind);
-  // beyond 256 / 288 tokens the attention forward streams K and V (attention_stream.hip); the backward stays at that range
+  // beyond 256 / 288 tokens the attention forward streams K and V (attention_stream.hip) and the backward streams too
+  // (attention_bwd_stream.hip): forward, classifier value-and-gradient and the eps-network VJP serve any H that max_tokens allows
   RGM_REQUIRE(c->max_tokens > 0 && c->max_tokens <= ATTN_STREAM_MAX_T, "dit_create: max_tokens %d (1..%d)", c->max_tokens, ATTN_STREAM_MAX_T);
   rgm_dit* h = new rgm_dit();
   h->cfg = *c;

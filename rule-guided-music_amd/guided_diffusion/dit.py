@@ -61,20 +61,49 @@ def _attach(root, dotted, param):
     mod.register_parameter(leaf, param)
 
 
-# Token counts the attention BACKWARD covers (csrc/attention_bwd.hip: K / V of a head in LDS), by head_dim.  The forward streams K and V
-# and runs up to 8192 tokens; everything that differentiates through a network (classifier guidance, DPS, guided editing) stays here.
+# Token counts the RESIDENT attention backward covers (csrc/attention_bwd.hip: K / V of a head in LDS), by head_dim.  The forward streams K
+# and V and runs up to 8192 tokens.  Everything that differentiates through a network (classifier guidance, DPS, guided editing) stops at
+# these counts BY DEFAULT and runs beyond them, up to LONG_BACKWARD_MAX_TOKENS (the cls token counts), once long guidance is switched on:
+# set_long_backward(True) or RGM_LONG_BACKWARD=1.  Then the streaming backward (csrc/attention_bwd_stream.hip) takes the lengths the
+# resident kernels cannot hold.  The switch is explicit because a guided step keeps every block's activations for the backward -- 40 x
+# hidden bytes per token and block in fp32 (1.29 MB per token for XL-28: 5.3 GB at 4096 tokens) -- and the workspace grows silently.
 BACKWARD_MAX_TOKENS = {72: 256, 64: 288}
+LONG_BACKWARD_MAX_TOKENS = 8192
+_LONG_BACKWARD = None     # None: follow the environment (read at every check, not at import)
+
+
+def set_long_backward(on):
+    """Switch guidance / DPS / guided editing beyond 256 / 288 tokens on or off; returns the previous setting.  None hands the
+    decision back to the environment (RGM_LONG_BACKWARD)."""
+    global _LONG_BACKWARD
+    prev = long_backward()
+    _LONG_BACKWARD = None if on is None else bool(on)
+    return prev
+
+
+def long_backward():
+    """True when long guidance is on: set_long_backward(True), else RGM_LONG_BACKWARD=1 in the environment."""
+    if _LONG_BACKWARD is not None:
+        return _LONG_BACKWARD
+    return os.environ.get("RGM_LONG_BACKWARD", "0").strip() not in ("", "0")
 
 
 def require_backward_tokens(n_tokens, head_dim, what):
     """NotImplementedError (before any launch) when `what` would need the attention backward beyond its range."""
     limit = BACKWARD_MAX_TOKENS.get(head_dim, 256)
+    if long_backward() and head_dim in BACKWARD_MAX_TOKENS:
+        if n_tokens > LONG_BACKWARD_MAX_TOKENS:
+            raise NotImplementedError(
+                f"{what} differentiates through the network, and the streaming attention backward supports at most "
+                f"{LONG_BACKWARD_MAX_TOKENS} tokens; this input has {n_tokens} tokens.")
+        return
     if n_tokens > limit:
         raise NotImplementedError(
             f"{what} differentiates through the network, and the attention backward supports at most {limit} tokens at head_dim "
             f"{head_dim} (a latent of height {limit // 2} at patch 8); this input has {n_tokens} tokens.  Unguided sampling, "
             "classifier-free guidance and SCG run at any length up to 8192 tokens; for guided long excerpts use DiffCollage "
-            "(diff_collage/, overlapping 128-wide windows).")
+            "(diff_collage/, overlapping 128-wide windows).  Guidance up to 8192 tokens is opt-in: "
+            "guided_diffusion.dit.set_long_backward(True) or RGM_LONG_BACKWARD=1.")
 
 
 class _NativeDiT(nn.Module):

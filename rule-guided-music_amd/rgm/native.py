@@ -91,6 +91,8 @@ def _load():
         "rgm_set_dit_halves": (C.c_int, [i32, vp]),
         "rgm_set_attn_pairs": (C.c_int, [i32]),
         "rgm_set_attn_stream": (C.c_int, [i32]),
+        "rgm_set_attn_bwd_stream": (C.c_int, [i32]),
+        "rgm_attn_bwd_stream_launches": (C.c_longlong, []),
         "rgm_set_gn_fuse": (C.c_int, [i32, vp]),
         "rgm_gn_fused_launches": (C.c_longlong, []),
         "rgm_gn_fallback_tiles": (C.c_longlong, [i32]),

@@ -99,6 +99,8 @@ def write_run_metadata(save_dir, args, extra=None):
     import json
     meta = {"config_path": args.config_path, "dropped_rules": list(DROPPED_RULES), "synthetic_weights": bool(args.synthetic_weights),
             "targets_npz": getattr(args, "targets_npz", "") or None}
+    from guided_diffusion.dit import long_backward
+    meta["long_backward"] = bool(long_backward())     # RGM_LONG_BACKWARD / set_long_backward: guidance beyond 256 / 288 tokens was allowed
     meta.update(extra or {})
     with open(os.path.join(save_dir, "run_metadata.json"), "w") as f:
         json.dump(meta, f, indent=1)

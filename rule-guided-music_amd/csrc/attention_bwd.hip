@@ -265,17 +265,20 @@ __global__ __launch_bounds__(512) void attn_bwd_dq_kernel(const float* __restric
       const float dstar = wave_sum(dpart);
       const float lq = lse[((long long)n * heads + head) * T + qs_];
       for (int key = lane; key < TP; key += 64) {
-        float sacc = 0.f, dpa = 0.f;
+        // the score in double (exact products, one rounding when s - lse becomes a float): a float tree rounds three times at the size of
+        // the largest term where the MFMA rows round once, and at |s| = 150 (ulp 1.5e-5) sum_key dS . K showed it (tests/attn_cases.py, rowshift)
+        double sacc = 0.0;
+        float dpa = 0.f;
         if (key < T) {
 #pragma unroll 4
           for (int d0 = 0; d0 < HD; d0 += 4) {
             const float4 kq = img_ld4<HD, X3>(Ks, key, d0), vq = img_ld4<HD, X3>(Vs, key, d0);
             const float4 qq = *reinterpret_cast<const float4*>(qrow + d0), gq = *reinterpret_cast<const float4*>(grow + d0);
-            sacc += (kq.x * qq.x + kq.y * qq.y) + (kq.z * qq.z + kq.w * qq.w);
+            sacc += ((double)kq.x * qq.x + (double)kq.y * qq.y) + ((double)kq.z * qq.z + (double)kq.w * qq.w);
             dpa += (vq.x * gq.x + vq.y * gq.y) + (vq.z * gq.z + vq.w * gq.w);
           }
         }
-        dsr[key] = key < T ? exp_le0(sacc - lq) * (dpa - dstar) : 0.f;
+        dsr[key] = key < T ? exp_le0((float)(sacc - (double)lq)) * (dpa - dstar) : 0.f;
       }
       for (int d = lane; d < HD; d += 64) {        // (same wave wrote dsr: LDS operations of a wave are in order)
         float a = 0.f;
@@ -584,17 +587,18 @@ __global__ __launch_bounds__(512) void attn_bwd_dkv_kernel(const float* __restri
         *reinterpret_cast<float4*>(vrow + d0) = *reinterpret_cast<const float4*>(rowp + 2 * D + d0);
       }
       for (int qi = lane; qi < TP; qi += 64) {
-        float sacc = 0.f, dpa = 0.f;
+        double sacc = 0.0;                       // the score in double, like the lone query of the dq kernel
+        float dpa = 0.f;
         if (qi < T) {
 #pragma unroll 4
           for (int d0 = 0; d0 < HD; d0 += 4) {
             const float4 qq = img_ld4<HD, X3>(Qs, qi, d0), gq = img_ld4<HD, X3>(Gs, qi, d0);
             const float4 kq = *reinterpret_cast<const float4*>(krow + d0), vq = *reinterpret_cast<const float4*>(vrow + d0);
-            sacc += (qq.x * kq.x + qq.y * kq.y) + (qq.z * kq.z + qq.w * kq.w);
+            sacc += ((double)qq.x * kq.x + (double)qq.y * kq.y) + ((double)qq.z * kq.z + (double)qq.w * kq.w);
             dpa += (gq.x * vq.x + gq.y * vq.y) + (gq.z * vq.z + gq.w * vq.w);
           }
         }
-        const float pv = qi < T ? exp_le0(sacc - Ls[qi]) : 0.f;
+        const float pv = qi < T ? exp_le0((float)(sacc - (double)Ls[qi < T ? qi : 0])) : 0.f;
         pr[qi] = pv;
         dsr[qi] = pv * (dpa - Ds[qi < T ? qi : 0]);
       }

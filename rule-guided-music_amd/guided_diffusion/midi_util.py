@@ -47,7 +47,7 @@ def decode_sample_for_midi(sample, embed_model=None, scale_factor=1., threshold=
     exact (default FINAL_DECODE_EXACT = True): run this decode in exact-fp32 arithmetic (reference midi_util.py:42-64 is fp32)."""
     if exact is None:
         exact = FINAL_DECODE_EXACT
-    if embed_model is not None and hasattr(embed_model, "decode_latent") and sample.shape[-2] >= sample.shape[-1]:
+    if embed_model is not None and hasattr(embed_model, "decode_latent") and sample.shape[-2] > sample.shape[-1]:
         with _rgm.gemm_precision_scope("fp32" if exact else None):
             return embed_model.decode_latent(sample, scale_factor, want_u8=True, threshold=threshold, want_float=False)
     sample = sample / scale_factor

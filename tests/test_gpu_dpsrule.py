@@ -11,6 +11,7 @@ from test_gpu_sampler import SM, _diffusion, _dit, _inject, _model_fn
 
 pytestmark = pytest.mark.gpu
 F32 = np.float32
+VAE_VJP_TOL = {"fp32": 3e-5, "bf16x3": 3e-4, "bf16x3_presplit": 3e-4}         # d(latent) against the reference's autograd, norm-wise (tests/vae_cases.py imports it)
 
 
 def _vae(seed=2):
@@ -31,7 +32,7 @@ def test_decoder_vjp_matches_reference_autograd(precision):
     cot = np.random.RandomState(int(g["vjp.gseed"])).randn(2, 3, 128, 256).astype(F32)
     dl = vae.decode_latent_vjp(dev(cot))
     assert dl.shape == lat.shape
-    tol = 3e-5 if precision == "fp32" else 3e-4
+    tol = VAE_VJP_TOL[precision]
     assert rel(dl.cpu().numpy(), g["vjp.dlat"]) < tol
     # linear in the cotangent.  A power-of-two factor commutes with every rounding; what is left is the summation order of the
     # GroupNorm reductions' fp64 LDS atomics (last-bit differences, which a bf16 split can amplify to 2^-17 of an element)

@@ -10,6 +10,7 @@ from rgm import synth
 pytestmark = pytest.mark.gpu
 F32 = np.float32
 SM = dict(depth=2, hidden=384, heads=6, patch=8, in_ch=4, out_ch=4, num_classes=3)
+VAE_DECODE_TOL = {"fp32": 5e-5, "bf16x3": 5e-5, "bf16x3_presplit": 5e-5}      # decoded roll against the reference, norm-wise (tests/vae_cases.py imports it)
 
 
 def _dit(arch, seed, final_std=None, device_gen=False):
@@ -82,7 +83,7 @@ def test_vae_decoder_matches_reference_and_uint8_roll(precision):
     g = load_golden("vae_decoder")
     vae = _vae(int(g["seed"]))
     out = vae.decode(dev(g["z"]))
-    assert rel(out.cpu().numpy(), g["out"]) < 5e-5
+    assert rel(out.cpu().numpy(), g["out"]) < VAE_DECODE_TOL[precision]
     u8 = decode_sample_for_midi(dev(g["lat"]), embed_model=vae, scale_factor=1.2465, threshold=-0.95)
     assert u8.shape == (1, 128, 256, 3) and u8.dtype == torch.uint8
     # the integer stage itself is bit-exact: quantise the float roll with the oracle's quantiser

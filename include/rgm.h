@@ -230,6 +230,19 @@ int rgm_ddpm_step_learned_g(const float* x, const float* eps, const float* var_v
 int rgm_ddim_step(const float* x, const float* eps, const float* grad, const float* noise, const int64_t* t,
                   const float* const* tables_host, int clip_denoised, int t_end, float eta, float* sample,
                   float* pred_xstart, float* g_out, int N, int E, void* stream);
+/* One step of DPM-Solver++(2M) in data-prediction form (csrc/dpm.hip; no counterpart in the reference).  With lambda_i = 1/2 log(abar_i /
+ * (1 - abar_i)) and h = lambda_{i-1} - lambda_i, at chain index i = t[b]:
+ *   x0 = c1 x - c2 eps (clip), then condition_score exactly as rgm_ddim_step applies it when grad != NULL;
+ *   D = x0 + w1[i] (x0 - x0_prev), w1 = 1 / (2 r0), r0 = (lambda_i - lambda_{i+1}) / h; D = x0 when x0_prev is NULL, order == 1,
+ *       i == num_timesteps - 1 (no earlier estimate) or i == 0 (the target has abar = 1);
+ *   sample = cx[i] x + cd[i] D + [i != t_end] cn[i] noise; at i == 0 the sample is D itself, bit for bit.
+ * dpm_tables_host: HOST array of 4 DEVICE float32 tables of length num_timesteps -- cx, cd, w1, cn -- built by the caller in float64:
+ *   ODE: cx = sigma_s / sigma_t, cd = -alpha_s expm1(-h), cn = 0;  SDE: cx = sigma_s / sigma_t e^-h, cd = -alpha_s expm1(-2h),
+ *   cn = sigma_s sqrt(-expm1(-2h));  entry 0 (h = inf) is cx = 0, cd = 1, cn = 0.  tables_host as above (entries 0, 1 and 6 are read).
+ * noise NULL -> sample is the mean; pred_xstart receives x0 (the next step's x0_prev); g_out (N) or NULL receives cn[t]. */
+int rgm_dpmpp_step(const float* x, const float* eps, const float* grad, const float* x0_prev, const float* noise, const int64_t* t,
+                   const float* const* tables_host, const float* const* dpm_tables_host, int num_timesteps, int order,
+                   int clip_denoised, int t_end, float* sample, float* pred_xstart, float* g_out, int N, int E, void* stream);
 /* ddim_reverse_sample (:978-1014), the DDIM ODE towards noise (eta = 0): x0 = c1 x - c2 eps (clip); eps' = (c1 x - x0) / c2 (re-derived,
  * so a clip shows in it); sample = sqrt(abar_next) x0 + sqrt(1 - abar_next) eps', abar_next = alphas_cumprod[t + 1], 0 at the last index
  * t == num_timesteps - 1 (the chain length = the tables' length).  Evaluated in fp64 per element, stored as fp32. */

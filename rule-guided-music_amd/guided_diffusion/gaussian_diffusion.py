@@ -29,6 +29,10 @@ SCG / DPS score candidates with an eps-predicting network (as every shipped conf
 What takes an existing latent as its input runs on forwards of the frozen network alone, at every length the forward serves:
 ddim_reverse_sample / ddim_reverse_sample_loop (DDIM inversion, rgm_ddim_reverse_step) and _vb_terms_bpd, _prior_bpd, calc_bpd_loop
 (the variational bound in bits per dimension with the per-timestep x0 / eps errors: rgm_vb_terms, a deterministic two-stage reduction).
+
+Beyond the reference: dpmpp_sample / dpmpp_sample_loop(_progressive), DPM-Solver++(2M) -- a second-order multistep solver in data-prediction
+form, as the probability-flow ODE (eta = 0) or its SDE form (eta = 1) -- one rgm_dpmpp_step launch per step on coefficient tables built
+here in float64 (dpmpp_tables); meant for a logSNR-uniform chain (respace.space_timesteps "logsnrN").
 """
 import ctypes as C
 import enum
@@ -65,6 +69,34 @@ def get_named_beta_schedule(schedule_name, num_diffusion_timesteps):
 def betas_for_alpha_bar(num_diffusion_timesteps, alpha_bar, max_beta=0.999):
     T = num_diffusion_timesteps
     return np.array([min(1 - alpha_bar((i + 1) / T) / alpha_bar(i / T), max_beta) for i in range(T)])
+
+
+def dpmpp_tables(alphas_cumprod):
+    """float64 coefficient tables of DPM-Solver++(2M) on a chain with the given alphas_cumprod: {"ode" | "sde": (cx, cd, w1, cn)}, the step
+    from chain index i to i - 1 being x_{i-1} = cx[i] x + cd[i] D + cn[i] z, D = x0 + w1[i] (x0 - x0_prev).  With lambda = 1/2 log(abar /
+    (1 - abar)) and h = lambda_{i-1} - lambda_i:  ODE cx = sigma_s / sigma_t, cd = -alpha_s expm1(-h);  SDE cx = sigma_s / sigma_t e^-h,
+    cd = -alpha_s expm1(-2h), cn = sigma_s sqrt(-expm1(-2h));  w1 = 1 / (2 r0) = h / (2 (lambda_i - lambda_{i+1})), 0 at both ends.
+    The final step (i = 0: abar = 1 at the target, h = inf) is written down -- cx = 0, cd = 1, cn = 0 -- never computed by exp."""
+    ac = np.asarray(alphas_cumprod, dtype=np.float64)
+    T = len(ac)
+    lam = 0.5 * np.log(ac / (1.0 - ac))
+    out = {}
+    for mode in ("ode", "sde"):
+        cx, cd, w1, cn = np.zeros(T), np.zeros(T), np.zeros(T), np.zeros(T)
+        cd[0] = 1.0
+        if T > 1:
+            h = lam[:-1] - lam[1:]                          # h[i-1] belongs to the step i -> i-1
+            a_s, s_s, s_t = np.sqrt(ac[:-1]), np.sqrt(1.0 - ac[:-1]), np.sqrt(1.0 - ac[1:])
+            if mode == "ode":
+                cx[1:] = s_s / s_t
+                cd[1:] = -a_s * np.expm1(-h)
+            else:
+                cx[1:] = s_s / s_t * np.exp(-h)
+                cd[1:] = -a_s * np.expm1(-2.0 * h)
+                cn[1:] = s_s * np.sqrt(-np.expm1(-2.0 * h))
+            w1[1:-1] = 0.5 * h[:-1] / h[1:]                 # lambda_i - lambda_{i+1} = h of the step before
+        out[mode] = (cx, cd, w1, cn)
+    return out
 
 
 class ModelMeanType(enum.Enum):
@@ -1076,6 +1108,121 @@ class GaussianDiffusion:
         for final in self.ddim_sample_loop_progressive(
                 model, shape, noise=noise, clip_denoised=clip_denoised, denoised_fn=denoised_fn, t_end=t_end,
                 cond_fn=cond_fn, model_kwargs=model_kwargs, device=device, progress=progress, eta=eta,
+                embed_model=embed_model, scale_factor=scale_factor, guidance_kwargs=guidance_kwargs,
+                scg_kwargs=scg_kwargs, edit_kwargs=edit_kwargs, record=record):
+            pass
+        return final["sample"]
+
+    # ------------------------------------------------------------------ DPM-Solver++(2M): second-order multistep, ODE and SDE
+    def _dpm_tab(self, device, sde):
+        """The four float32 coefficient tables of one mode on the device + the host pointer array rgm_dpmpp_step takes."""
+        key = ("dpm_sde" if sde else "dpm_ode") + str(device)
+        if key not in self._tables:
+            tabs = dpmpp_tables(self.alphas_cumprod)["sde" if sde else "ode"]
+            tensors = [th.from_numpy(a).to(device=device, dtype=th.float32).contiguous() for a in tabs]
+            self._tables[key] = (tensors, (C.c_void_p * 4)(*[a.data_ptr() for a in tensors]))
+        return self._tables[key]
+
+    def _dpm_step(self, x, eps, grad, x0_prev, noise, t, clip_denoised, order=2, eta=0.0, want_g=False):
+        """One rgm_dpmpp_step launch -> (sample_or_mean, pred_xstart, g or None)."""
+        _rgm.require_cuda(x, eps, grad, x0_prev, noise, t)
+        x = x.float().contiguous()
+        eps = eps.float().contiguous()
+        assert eps.shape == x.shape, f"model output {tuple(eps.shape)} vs x {tuple(x.shape)}"
+        grad = None if grad is None else grad.float().contiguous()
+        noise = None if noise is None else noise.float().contiguous()
+        x0_prev = None if x0_prev is None else x0_prev.float().contiguous()
+        # the kernel indexes grad / x0_prev / noise like x (see _step)
+        assert grad is None or grad.shape == x.shape, f"cond_fn returned {tuple(grad.shape)}, expected a gradient like x {tuple(x.shape)}"
+        assert noise is None or noise.shape == x.shape, f"noise {tuple(noise.shape)} vs x {tuple(x.shape)}"
+        assert x0_prev is None or x0_prev.shape == x.shape, f"x0_prev {tuple(x0_prev.shape)} vs x {tuple(x.shape)}"
+        tt = t.long().contiguous()
+        N = x.shape[0]
+        assert tt.shape == (N,)
+        E = x.numel() // N
+        sample, x0 = th.empty_like(x), th.empty_like(x)
+        g = th.empty(N, dtype=th.float32, device=x.device) if want_g else None
+        with th.cuda.device(x.device):
+            _rgm.check(_rgm.lib.rgm_dpmpp_step(_rgm.ptr(x), _rgm.ptr(eps), _rgm.ptr(grad), _rgm.ptr(x0_prev), _rgm.ptr(noise), _rgm.ptr(tt),
+                                               self._tab(x.device).ptrs, self._dpm_tab(x.device, eta == 1)[1], int(self.num_timesteps),
+                                               int(order), int(bool(clip_denoised)), int(self.t_end), _rgm.ptr(sample), _rgm.ptr(x0),
+                                               _rgm.ptr(g), N, E, _rgm.current_stream()))
+        return sample, x0, g
+
+    def _dpmpp_check(self, order, eta, scg_kwargs):
+        """What the solver cannot do, refused by name before anything is computed."""
+        if eta not in (0, 1):
+            raise ValueError(f"dpmpp_sample: eta = {eta!r}; the solver has an ODE (eta = 0) and an SDE (eta = 1) form only")
+        if order not in (1, 2):
+            raise ValueError(f"dpmpp_sample: order = {order!r}; DPM-Solver++(2M) is second order (or 1: its first-order start)")
+        if self.model_mean_type == ModelMeanType.PREVIOUS_X:
+            raise NotImplementedError("dpmpp_sample: a PREVIOUS_X network predicts the ancestral mean x_{t-1}; the solver integrates a data "
+                                      "(x0) prediction and has no use for that mean")
+        if scg_kwargs is not None and eta == 0:
+            raise ValueError("dpmpp_sample: SCG branches on the noise of a stochastic step; eta = 0 (the ODE) has none -- use eta = 1")
+
+    def dpmpp_sample(self, model, x, t, x0_prev=None, order=2, eta=0.0, clip_denoised=True, denoised_fn=None, cond_fn=None,
+                     model_kwargs=None, embed_model=None, scale_factor=1., guidance_kwargs=None, edit_kwargs=None, scg_kwargs=None,
+                     record=False):
+        """One DPM-Solver++(2M) step -> {'sample', 'pred_xstart'}.  eta = 0: the probability-flow ODE; eta = 1: the SDE variant
+        (order 1 is then DDIM's eta = 1 step).  x0_prev: 'pred_xstart' of the step before, at chain index t + 1; None (or order = 1, the
+        chain's top index, the last index) makes the step first order.  Best on a "logsnrN" chain (respace.space_timesteps).
+        Every rank computes the whole batch (no batch sharding); the candidates of an SCG search step are sharded as ever."""
+        self._dpmpp_check(order, eta, scg_kwargs)
+        model_kwargs = model_kwargs or {}
+        use_guidance = self._use_guidance(guidance_kwargs, t)
+        if cond_fn is not None and use_guidance and getattr(guidance_kwargs, "method", None) == "dps":
+            raise NotImplementedError("DPS guidance is defined for the DDPM step (p_sample) only; dpmpp_sample applies "
+                                      "condition_score, which needs a gradient cond_fn")
+        wrapped = self._wrap_model(model)
+        if scg_kwargs is not None and use_guidance and self._t0(t) > self.t_end:
+            # a search step: mean and noise scale come from the kernel, the candidate search is ddim_sample's
+            eps, grad = self._search_step_inputs(model, cond_fn, x, t, model_kwargs, denoised_fn, edit_kwargs, clip_denoised, record,
+                                                 grad_on_edit_rows=False)
+            mean, x0, g = self._dpm_step(x, eps, grad, x0_prev, None, t, clip_denoised, order=order, eta=eta, want_g=True)
+            sample = self.scg_sample(wrapped, t, mean, g, embed_model, scale_factor, model_kwargs=model_kwargs,
+                                     scg_kwargs=scg_kwargs, edit_kwargs=edit_kwargs,
+                                     dc_kwargs=getattr(guidance_kwargs, "dc", None), record=record, record_freq=10)
+            return {"sample": sample, "pred_xstart": x0}
+        eps = self._model_eps(x, self._eps_net(wrapped, x, t, **model_kwargs), t, denoised_fn)   # learned sigma: the eps half
+        if edit_kwargs is not None:
+            eps = self._edit_eps(x, eps, t, clip_denoised, edit_kwargs, denoised_fn)
+        grad = None
+        if cond_fn is not None and use_guidance:
+            grad = self._wrap_model(cond_fn)(x, self._scale_timesteps(t), **model_kwargs)
+        noise = None
+        if eta == 1 and (scg_kwargs is None or self._t0(t) > self.t_end):
+            noise = self._draw(x.shape, x.device)
+        sample, x0, _ = self._dpm_step(x, eps, grad, x0_prev, noise, t, clip_denoised, order=order, eta=eta)
+        return {"sample": sample, "pred_xstart": x0}
+
+    def dpmpp_sample_loop_progressive(self, model, shape, noise=None, clip_denoised=True, denoised_fn=None, t_end=0,
+                                      cond_fn=None, model_kwargs=None, device=None, progress=False, order=2, eta=0.0,
+                                      embed_model=None, scale_factor=1., guidance_kwargs=None, scg_kwargs=None,
+                                      edit_kwargs=None, record=False):
+        """The chain of dpmpp_sample steps; each step's pred_xstart is the next one's x0_prev (the first step -- the top index, or
+        `noise_level` of an edit -- has none and is first order)."""
+        kw = dict(order=order, eta=eta, clip_denoised=clip_denoised, denoised_fn=denoised_fn, cond_fn=cond_fn, model_kwargs=model_kwargs,
+                  embed_model=embed_model, scale_factor=scale_factor, guidance_kwargs=guidance_kwargs,
+                  scg_kwargs=scg_kwargs, edit_kwargs=edit_kwargs, record=record)
+        self._dpmpp_check(order, eta, scg_kwargs)          # before the loop draws its start
+        carried = [None]
+
+        def step(model, img, t, **kwargs):
+            out = self.dpmpp_sample(model, img, t, x0_prev=carried[0], **kwargs)
+            carried[0] = out["pred_xstart"]
+            return out
+        yield from self._loop(step, model, shape, noise, t_end, device, progress, edit_kwargs, kw)
+
+    def dpmpp_sample_loop(self, model, shape, noise=None, clip_denoised=True, denoised_fn=None, t_end=0, cond_fn=None,
+                          model_kwargs=None, device=None, progress=False, order=2, eta=0.0, embed_model=None, scale_factor=1.,
+                          guidance_kwargs=None, scg_kwargs=None, edit_kwargs=None, record=False):
+        self.t_end = t_end
+        self._reset_records(record, shape, device)
+        final = None
+        for final in self.dpmpp_sample_loop_progressive(
+                model, shape, noise=noise, clip_denoised=clip_denoised, denoised_fn=denoised_fn, t_end=t_end,
+                cond_fn=cond_fn, model_kwargs=model_kwargs, device=device, progress=progress, order=order, eta=eta,
                 embed_model=embed_model, scale_factor=scale_factor, guidance_kwargs=guidance_kwargs,
                 scg_kwargs=scg_kwargs, edit_kwargs=edit_kwargs, record=record):
             pass

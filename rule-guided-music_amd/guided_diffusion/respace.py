@@ -11,10 +11,33 @@ import torch as th
 from .gaussian_diffusion import GaussianDiffusion
 
 
-def space_timesteps(num_timesteps, section_counts):
-    """Set of kept original timesteps.  "ddimN": fixed integer stride giving exactly N steps;
+def logsnr_timesteps(alphas_cumprod, count):
+    """Timesteps nearest to `count` targets spaced uniformly in lambda_t = 1/2 log(abar_t / (1 - abar_t)) (float64) between
+    lambda_0 and lambda_{T-1}: the spacing a multistep solver in lambda wants (dpmpp_sample).  The lower t wins a tie, duplicates
+    merge (the chain can be shorter than `count`), t = 0 and t = T - 1 are always kept."""
+    ac = np.asarray(alphas_cumprod, dtype=np.float64)
+    T = len(ac)
+    if count < 2 or count > T:
+        raise ValueError(f"cannot place {count} logSNR-uniform steps on a chain of {T}")
+    lam = 0.5 * np.log(ac / (1.0 - ac))
+    kept = {0, T - 1}
+    for target in np.linspace(lam[0], lam[-1], count):
+        kept.add(int(np.argmin(np.abs(lam - target))))      # argmin returns the first (lowest t) of equal distances
+    return kept
+
+
+def space_timesteps(num_timesteps, section_counts, betas=None):
+    """Set of kept original timesteps.  "ddimN": fixed integer stride giving exactly N steps; "logsnrN": N targets uniform in
+    logSNR on the schedule `betas` (the linear schedule of num_timesteps steps when not given), see logsnr_timesteps;
     otherwise comma-separated (or list of) per-section counts with rounded fractional strides."""
     if isinstance(section_counts, str):
+        if section_counts.startswith("logsnr"):
+            if betas is None:
+                from .gaussian_diffusion import get_named_beta_schedule
+                betas = get_named_beta_schedule("linear", num_timesteps)
+            betas = np.asarray(betas, dtype=np.float64)
+            assert len(betas) == num_timesteps
+            return logsnr_timesteps(np.cumprod(1.0 - betas), int(section_counts[len("logsnr"):]))
         if section_counts.startswith("ddim"):
             want = int(section_counts[len("ddim"):])
             for stride in range(1, num_timesteps):

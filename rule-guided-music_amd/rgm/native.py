@@ -45,6 +45,7 @@ def _load():
         "rgm_ddpm_step_learned_g": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, vp, vp, vp, i32, i32, vp]),
         "rgm_scg_rebuild_g": (C.c_int, [vp, vp, vp, C.c_uint64, C.c_uint64, vp, i32, i32, i32, i32, i32, vp]),
         "rgm_ddim_step": (C.c_int, [vp, vp, vp, vp, vp, vp, i32, i32, f32, vp, vp, vp, i32, i32, vp]),
+        "rgm_dpmpp_step": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, i32, i32, vp]),
         "rgm_ddim_reverse_step": (C.c_int, [vp, vp, vp, vp, i32, i32, vp, vp, i32, i32, vp]),
         "rgm_vb_terms_partials": (C.c_int64, [i32, i32]),
         "rgm_vb_terms": (C.c_int, [vp] * 12 + [i32, vp, vp, vp, vp, vp, i32, i32, vp]),

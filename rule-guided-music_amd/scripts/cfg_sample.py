@@ -5,7 +5,7 @@ Every rank draws its own batches (class-conditional, the null label, or classifi
 evaluated as ONE forward of 2B rows: condition_functions.model_fn), decodes them to uint8 piano rolls on the device, and the
 rolls -- 0.4 MB per sample -- are all-gathered (RCCL; the only collective) so that rank 0 writes the MIDI / .npy files.
 Flags and defaults are the reference's (:130-157); additions: --synthetic_weights (no checkpoints offline), --seed,
---gemm_precision, --progress.  Ranks use different Philox streams (seed + rank): unlike the sharded SCG of sample_rule.py,
+--gemm_precision, --progress, --use_dpmpp (DPM-Solver++(2M) on --dpmpp_steps logSNR-uniform steps, --dpmpp_order, --dpmpp_eta).  Ranks use different Philox streams (seed + rank): unlike the sharded SCG of sample_rule.py,
 where all ranks must share one stream, here they must NOT produce the same samples.
 
     torchrun --nnodes=1 --nproc-per-node 8 scripts/cfg_sample.py --model_path ... --cfg True --w 4. --class_label 1
@@ -39,6 +39,8 @@ def main(argv=None):
     world = dist.get_world_size() if dist.is_initialized() else 1
     rank = dist.get_rank() if dist.is_initialized() else 0
 
+    if args.use_dpmpp:      # DPM-Solver++(2M) on --dpmpp_steps logSNR-uniform steps instead of the DDPM / DDIM chain
+        args.timestep_respacing = f"logsnr{int(args.dpmpp_steps)}"
     logger.log("creating model and diffusion...")
     model = DiT_models[args.model](input_size=args.image_size, in_channels=args.in_channels, num_classes=args.num_classes,
                                    learn_sigma=args.learn_sigma)
@@ -71,6 +73,13 @@ def main(argv=None):
     os.makedirs(os.path.expanduser(save_dir), exist_ok=True)
     shape = (args.batch_size, args.in_channels, args.image_size[0], args.image_size[1])
     sample_fn = diffusion.p_sample_loop if not args.use_ddim else diffusion.ddim_sample_loop
+    if args.use_dpmpp:
+        sample_fn = partial(diffusion.dpmpp_sample_loop, order=int(args.dpmpp_order), eta=float(args.dpmpp_eta))
+        if rank == 0:
+            import json
+            with open(os.path.join(save_dir, "run_metadata.json"), "w") as f:
+                json.dump({"sampler": {"name": "dpmpp", "timestep_respacing": args.timestep_respacing, "steps": int(args.dpmpp_steps),
+                                       "order": int(args.dpmpp_order), "eta": float(args.dpmpp_eta)}}, f, indent=1)
     rolls, labels = [], []
     while len(rolls) * args.batch_size < args.num_samples:
         model_kwargs = {}
@@ -130,6 +139,7 @@ def create_argparser():
         training=False, port=None,
         # additions of this implementation
         synthetic_weights=False, progress=True, gemm_precision="bf16x3_presplit", seed=0,
+        use_dpmpp=False, dpmpp_steps=20, dpmpp_order=2, dpmpp_eta=1.0,
     )
     defaults.update(model_and_diffusion_defaults())
     parser = argparse.ArgumentParser()

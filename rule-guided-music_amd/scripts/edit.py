@@ -111,6 +111,16 @@ def edit_target_rules(target_rules, gt_partial, batch_size, device):
     return out, orig
 
 
+def dpmpp_noise_level(args, config, diffusion, noise_level):
+    """edit.noise_level counts steps of the YAML's chain; --sampler dpmpp runs another chain of the same schedule.  -> the number of
+    its steps at or below the timestep the YAML's chain would start from (at least 1): the edit starts at the same noise."""
+    from guided_diffusion.respace import space_timesteps
+    rs = config.sampling.timestep_respacing if config.sampling.use_ddim else ""
+    theirs = sorted(space_timesteps(args.diffusion_steps, rs if rs else [args.diffusion_steps]))
+    t_start = theirs[min(max(noise_level, 1), len(theirs)) - 1]
+    return max(1, sum(1 for t in diffusion.timestep_map if t <= t_start))
+
+
 LAST_START = None      # the start latent of the last run under --edit_start ddim_inversion (None: the loop drew its own)
 
 
@@ -131,8 +141,7 @@ def main(argv=None):
     if args.edit_start == "ddim_inversion":
         args.dir += "_inv"
     logger.configure(args=args, comm=comm)
-    if config.sampling.use_ddim:
-        args.timestep_respacing = config.sampling.timestep_respacing
+    _sr.choose_sampler(args, config)
     device = dist_util.dev()
     rank0 = int(os.environ.get("RANK", "0")) == 0
     if args.vae is None:
@@ -146,14 +155,16 @@ def main(argv=None):
     save_dir = logger.get_dir()
     save_dir_gt = os.path.join(save_dir, "gt")
     os.makedirs(os.path.expanduser(save_dir_gt), exist_ok=True)
-    sample_fn = partial(diffusion.ddim_sample_loop, eta=1.) if config.sampling.use_ddim else diffusion.p_sample_loop
+    sample_fn = _sr.sampler_loop(args, config, diffusion)
 
     edit_kwargs = dict(vars(config.edit))
+    if args.sampler == "dpmpp":
+        edit_kwargs["noise_level"] = dpmpp_noise_level(args, config, diffusion, int(edit_kwargs["noise_level"]))
     edit_kwargs["l_start_pix"], edit_kwargs["l_end_pix"] = edit_kwargs["l_start"] * 8, edit_kwargs["l_end"] * 8
     gt = load_source(edit_kwargs.get("source", "synthetic"), gen_shape[2] * 8, args.fs, device, allow_synthetic=args.allow_synthetic_source)
     if args.save_files and rank0:
         _sr.write_run_metadata(save_dir, args, {"source": edit_kwargs.get("source", "synthetic"), "source_substituted_by_synthetic": bool(substituted),
-                                                   "edit_start": args.edit_start})
+                                                   "edit_start": args.edit_start, "noise_level": int(edit_kwargs["noise_level"])})
     gt_latent = _encode(gt, embed_model, scale_factor=args.scale_factor)
     mask = th.ones_like(gt_latent)
     mask[:, :, edit_kwargs["l_start"]:edit_kwargs["l_end"], :] = 0.
@@ -212,7 +223,7 @@ def main(argv=None):
 
 
 def create_argparser():
-    parser = _sample_argparser()
+    parser = _sr.add_sampler_arguments(_sample_argparser())
     parser.add_argument("--allow_synthetic_source", default=False, type=lambda v: str(v).lower() in ("yes", "true", "t", "y", "1"),
                         help="edit.source 'dataset' needs the reference's data loader; True substitutes a seeded synthetic roll "
                              "(marked in the output directory name and run_metadata.json)")

@@ -100,10 +100,38 @@ def write_run_metadata(save_dir, args, extra=None):
     meta = {"config_path": args.config_path, "dropped_rules": list(DROPPED_RULES), "synthetic_weights": bool(args.synthetic_weights),
             "targets_npz": getattr(args, "targets_npz", "") or None}
     from guided_diffusion.dit import long_backward
+    meta["sampler"] = sampler_metadata(args)
     meta["long_backward"] = bool(long_backward())     # RGM_LONG_BACKWARD / set_long_backward: guidance beyond 256 / 288 tokens was allowed
     meta.update(extra or {})
     with open(os.path.join(save_dir, "run_metadata.json"), "w") as f:
         json.dump(meta, f, indent=1)
+
+
+def choose_sampler(args, config):
+    """The chain of this run, set in args.timestep_respacing before the diffusion is built.  --sampler config: what the YAML says (DDIM
+    with eta = 1 on sampling.timestep_respacing when sampling.use_ddim, else the DDPM chain).  --sampler dpmpp: DPM-Solver++(2M) on
+    --dpmpp_steps logSNR-uniform steps of the same schedule, whatever chain the YAML names."""
+    if args.sampler not in ("config", "dpmpp"):
+        raise ValueError(f"--sampler {args.sampler!r}: 'config' (the YAML's DDPM / DDIM chain) or 'dpmpp'")
+    if config.sampling.use_ddim:
+        args.timestep_respacing = config.sampling.timestep_respacing
+    if args.sampler == "dpmpp":
+        args.timestep_respacing = f"logsnr{int(args.dpmpp_steps)}"
+
+
+def sampler_loop(args, config, diffusion):
+    """The sampling loop choose_sampler picked, with the sampler's own arguments bound."""
+    if args.sampler == "dpmpp":
+        return partial(diffusion.dpmpp_sample_loop, order=int(args.dpmpp_order), eta=float(args.dpmpp_eta))
+    return partial(diffusion.ddim_sample_loop, eta=1.) if config.sampling.use_ddim else diffusion.p_sample_loop
+
+
+def sampler_metadata(args):
+    name = getattr(args, "sampler", "config")
+    if name != "dpmpp":
+        return {"name": "config", "timestep_respacing": getattr(args, "timestep_respacing", "")}
+    return {"name": "dpmpp", "timestep_respacing": args.timestep_respacing, "steps": int(args.dpmpp_steps),
+            "order": int(args.dpmpp_order), "eta": float(args.dpmpp_eta)}
 
 
 def targets_from_npz(path, target_rules, batch_size, device):
@@ -268,7 +296,7 @@ def build_pipeline(args, config, device):
 
 
 def main(argv=None):
-    args = create_argparser().parse_args(argv)
+    args = add_sampler_arguments(create_argparser()).parse_args(argv)
     args.dir = output_dir_for(args.config_path, args.class_label)
     from rgm import native as _native
     _native.set_gemm_precision(args.gemm_precision)      # "bf16x3_presplit" / "bf16x3" (fast, fp32-grade) or "fp32" (exact fp32 MFMA)
@@ -277,8 +305,7 @@ def main(argv=None):
     if DROPPED_RULES:
         args.dir += "_nochord"
     logger.configure(args=args, comm=comm)
-    if config.sampling.use_ddim:
-        args.timestep_respacing = config.sampling.timestep_respacing
+    choose_sampler(args, config)
     device = dist_util.dev()
     rank0 = int(os.environ.get("RANK", "0")) == 0
 
@@ -305,7 +332,7 @@ def main(argv=None):
     os.makedirs(os.path.expanduser(save_dir), exist_ok=True)
     if args.save_files and rank0:
         write_run_metadata(save_dir, args)
-    sample_fn = partial(diffusion.ddim_sample_loop, eta=1.) if config.sampling.use_ddim else diffusion.p_sample_loop
+    sample_fn = sampler_loop(args, config, diffusion)
     use_scg = bool(getattr(config.guidance, "scg", getattr(config.guidance, "beam", False)))
 
     logger.log("sampling...")
@@ -362,6 +389,20 @@ def create_argparser():
     defaults.update(model_and_diffusion_defaults())
     parser = argparse.ArgumentParser()
     add_dict_to_argparser(parser, defaults)
+    return parser
+
+
+def add_sampler_arguments(parser):
+    """--sampler and the DPM-Solver++ options: one group for sample_rule.py and edit.py, with the choices and help texts that the
+    defaults dictionary of create_argparser (the reference's flags) cannot carry."""
+    g = parser.add_argument_group("sampler")
+    g.add_argument("--sampler", default="config", choices=["config", "dpmpp"],
+                   help="'config': the YAML's chain (DDPM, or DDIM with eta = 1 on sampling.timestep_respacing); 'dpmpp': DPM-Solver++(2M) "
+                        "on --dpmpp_steps logSNR-uniform steps of the same schedule")
+    g.add_argument("--dpmpp_steps", type=int, default=20, help="targets of the logSNR-uniform chain (timestep_respacing 'logsnrN')")
+    g.add_argument("--dpmpp_order", type=int, default=2, choices=[1, 2], help="2: the multistep solver; 1: first order throughout")
+    g.add_argument("--dpmpp_eta", type=float, default=1.0, choices=[0.0, 1.0],
+                   help="1: the SDE form (stochastic; what SCG needs to have candidates); 0: the probability-flow ODE")
     return parser
 
 

@@ -354,6 +354,23 @@ int rgm_rule_note_density(float* roll, float* out, int N, int C, int T, int inte
 /* get_chords' preamble (music_rules.py:97-110): piano_like mask and < -0.95 -> -1 written into channel 0 of roll, then
  * clamp((x+1)/2*127, 0, 127) truncated -> out (N,128,T) uint8: the integer roll the host chord analyser (music21) reads. */
 int rgm_rule_chord_quantise(float* roll, uint8_t* out, int N, int C, int T, void* stream);
+/* The native chord and key analyser of the chord rules, on the integer roll q (N,128,T) uint8 of rgm_rule_chord_quantise.  Its own
+ * definition (docs/rounds/chords.md), NOT a restatement of the reference's music21 analyser: agreement with music21 is unmeasured.
+ *   active(p,t) = q[p,t] > 0 for the piano pitches 21..108 only; W = T / Wc windows of Wc columns (1 <= Wc <= 1024), the columns
+ *   behind W*Wc count for the key only.
+ *   key: D[c] = number of active (p,t) with p % 12 == c over all T columns; r_k = Pearson correlation (float64, sums in class order
+ *     0..11, no FMA contraction) of D with profile[mode][(c - tonic) % 12] for k = 12*mode + tonic (mode 0 = major); the key is the
+ *     first maximum, coef = r_key; sum (D - mean)^2 == 0 (silence, flat profile): key -1, coef 0, all chords 0.
+ *   window chord: the longest maximal run of columns with one non-empty set of active pitches (runs cut at window boundaries, the
+ *     earliest among equals); its root r maximises 8[r+7] + 4[r+4 or r+3] + 3[r+6] + 2[r+10 or r+11] over its pitch classes (membership
+ *     mod 12), ties to the smallest (r - bass) % 12; roots[n][w] = r, or -1 without a sounding column.
+ *   chords[n][w] = DEG[(root - tonic) % 12], DEG = 1 2 2 3 3 4 4 5 6 6 7 7, 0 for a silent window.  tonic = given_tonic[n] (0..11)
+ *     where given_tonic != NULL and >= 0, else the analysed key's.  analyse_key == 0 (needs given_tonic): no key analysis, key -1 and
+ *     coef 0 are written, a sample with given_tonic < 0 gets chords 0.
+ * profile: 2 x 12 doubles [major | minor] on the device.  chords (N,W) int64, roots (N,W) int32, key (N) int32, coef (N) float64.
+ * ws: N * (T / Wc + 1) * 12 int32.  Two launches, no atomics: bitwise repeatable, a sample's answer independent of N and its row. */
+int rgm_rule_chords(const uint8_t* q, int N, int T, int Wc, const double* profile, const int32_t* given_tonic, int analyse_key,
+                    int64_t* chords, int32_t* roots, int32_t* key, double* coef, void* ws, size_t ws_bytes, void* stream);
 /* torch.bucketize(v, bounds) as used by note_density_class (:86-94): out int64. */
 int rgm_bucketize(const float* v, const float* bounds, int nb, int64_t* out, int n, void* stream);
 /* mse_loss_mean / zero_one_loss_mean (rule_maps.py:17-22) over the last dim: a,b (rows,K) -> out (rows). */

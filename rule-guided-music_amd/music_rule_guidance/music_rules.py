@@ -94,27 +94,85 @@ def note_density_class(piano_roll, interval=128, quantize_factor=1, horizontal_s
     return out.to(piano_roll.device)
 
 
-# ---- chord rule (a11): device-side preamble + a host analyser.  The reference's analyser is symbolic-music code on music21
+# ---- chord rule (a11): device-side preamble + an analyser.  The reference's analyser is symbolic-music code on music21
 # (piano_roll_to_chord.py:307-359), which is not vendored and cannot be restated: it stays a plug-in with the reference's own
 # per-excerpt signature, so `register_chord_backend(piano_roll_to_chords)` with the reference's function is all a user with
-# music21 needs.  What IS arithmetic on the roll -- mask, background snap, 0..127 quantisation -- runs on the GPU.
+# music21 needs.  What IS arithmetic on the roll -- mask, background snap, 0..127 quantisation -- runs on the GPU.  Opt-in beside it:
+# `register_chord_backend("native")`, an analyser with its own definition that scores the integer roll on the device (csrc/chords.hip).
 KEY_DICT = {"D major": 0, "g minor": 1, "B- major": 2, "G major": 3, "d minor": 4, "c# minor": 5, "F major": 6, "E- major": 7,
             "e minor": 8, "f# minor": 9, "C major": 10, "F# major": 11, "g# minor": 12, "A major": 13, "a minor": 14,
             "B major": 15, "A- major": 16, "b- minor": 17, "E major": 18, "c minor": 19, "b minor": 20, "e- minor": 21,
             "f minor": 22, "C# major": 23, "no key": 24}      # the chord classifier's key classes (piano_roll_to_chord.py:15-18)
 IND2KEY = {v: k for k, v in KEY_DICT.items()}
 
+# ---- the native analyser's tables (docs/rounds/chords.md: its own definition, agreement with music21 unmeasured).  Key number
+# k = 12 * mode + tonic, mode 0 = major, tonic 0 = C; the device kernel (csrc/chords.hip) and the host analyser
+# (piano_roll_to_chord.piano_roll_to_chords_native) both read these.
+CHORD_KEY_NAMES = [t + " major" for t in ("C", "C#", "D", "E-", "E", "F", "F#", "G", "A-", "A", "B-", "B")] + \
+                  [t + " minor" for t in ("c", "c#", "d", "e-", "e", "f", "f#", "g", "g#", "a", "b-", "b")]
+CHORD_PROFILES = {
+    "krumhansl": ((6.35, 2.23, 3.48, 2.33, 4.38, 4.09, 2.52, 5.19, 2.39, 3.66, 2.29, 2.88),                 # Krumhansl & Kessler 1982
+                  (6.33, 2.68, 3.52, 5.38, 2.60, 3.53, 2.54, 4.75, 3.98, 2.69, 3.34, 3.17)),
+    "aarden": ((17.7661, 0.145624, 14.9265, 0.160186, 19.8049, 11.3587, 0.291248, 22.062, 0.145624, 8.15494, 0.232998, 4.95122),
+               (18.2648, 0.737619, 14.0499, 16.8599, 0.702494, 14.4362, 0.702494, 18.6161, 4.56621, 1.93186, 7.37619, 1.75623)),
+}
+CHORD_DEGREES = (1, 2, 2, 3, 3, 4, 4, 5, 6, 6, 7, 7)      # scale degree of (root - tonic) % 12: an altered degree carries its numeral's number
+CHORD_MAX_WINDOW = 1024                                    # columns per window the kernel holds in LDS
+
+
+def chord_profile(name):
+    if name not in CHORD_PROFILES:
+        raise ValueError(f"chord profile {name!r}: one of {sorted(CHORD_PROFILES)}")
+    return CHORD_PROFILES[name]
+
+
+def chord_window_columns(fs, window_size):
+    """columns per chord window, window_size * fs: an integer (within 1e-9) in 1 .. 1024, else ValueError"""
+    wc = float(window_size) * float(fs)
+    n = int(round(wc))
+    if abs(wc - n) > 1e-9 or not 1 <= n <= CHORD_MAX_WINDOW:
+        raise ValueError(f"chord window of window_size * fs = {window_size} * {fs} = {wc} columns: must be an integer in 1 .. {CHORD_MAX_WINDOW}")
+    return n
+
+
+def parse_key(key):
+    """'C major', 'b- minor', 'c#', 'Bb' ... -> tonic pitch class 0..11: a letter, an optional '#' or '-' / 'b', an optional mode word
+    (the degree table is the same for both modes, so only the tonic matters).  Anything else: ValueError."""
+    import re
+    m = re.fullmatch(r"\s*([A-Ga-g])([#\-b]?)(?:\s+([A-Za-z]+))?\s*", key) if isinstance(key, str) else None
+    if m is None or (m.group(3) is not None and m.group(3).lower() not in ("major", "minor")):
+        raise ValueError(f"key {key!r}: expected a letter, an optional '#' or '-' / 'b' and an optional 'major' / 'minor'")
+    pc = {"c": 0, "d": 2, "e": 4, "f": 5, "g": 7, "a": 9, "b": 11}[m.group(1).lower()]
+    return (pc + {"": 0, "#": 1, "-": -1, "b": -1}[m.group(2)]) % 12
+
+
+def key_class(k):
+    """key number of the native analyser (-1: none) -> the chord classifier's key class (KEY_DICT)"""
+    return KEY_DICT["no key"] if k < 0 else KEY_DICT[CHORD_KEY_NAMES[k]]
+
+
 _CHORD_BACKEND = None
 _CHORD_WORKERS = 4          # the reference chunks the batch over a 4-process pool (gaussian_diffusion.py:1365-1371)
 _CHORD_POOL = None
+_CHORD_PROFILE = "krumhansl"   # key profiles of the "native" backend
+_PROFILE_DEV = {}           # (device, profile) -> (2,12) float64 tensor
 
 
-def register_chord_backend(fn, workers=4):
+def register_chord_backend(fn, workers=4, profile="krumhansl"):
     """fn(piano_roll (128,T) int array in [0,127], given_key=None, return_key=False, fs=100., window_size=1.28) ->
     {"chords": LongTensor (T/fs/window_size,), ["key": int, "correlationCoefficient": float]} -- the signature of the reference's
     piano_roll_to_chords (music21).  workers > 1 evaluates the excerpts of a batch in a persistent spawn-context process pool
-    (fn must be picklable, i.e. a module-level function); 0/1 = in this process."""
-    global _CHORD_BACKEND, _CHORD_WORKERS, _CHORD_POOL
+    (fn must be picklable, i.e. a module-level function); 0/1 = in this process.
+
+    fn = "native": the analyser on the device (chords_native below; `profile` = "krumhansl" | "aarden" picks its key profiles; no
+    workers, no host round trip).  It follows its own definition (docs/rounds/chords.md), as does its host partner
+    piano_roll_to_chord.piano_roll_to_chords_native, which registers like any other function; agreement of either with music21 has
+    not been measured."""
+    global _CHORD_BACKEND, _CHORD_WORKERS, _CHORD_POOL, _CHORD_PROFILE
+    if isinstance(fn, str) and fn != "native":
+        raise ValueError(f"chord backend {fn!r}: a function, or 'native' for the device analyser")
+    chord_profile(profile)
+    _CHORD_PROFILE = profile
     if _CHORD_POOL is not None:
         _CHORD_POOL.terminate()
         _CHORD_POOL = None
@@ -131,6 +189,55 @@ def chord_quantise(piano_roll_batch):
         _rgm.check(_rgm.lib.rgm_rule_chord_quantise(_rgm.ptr(d), _rgm.ptr(q), N, Cc, T, _rgm.current_stream()))
     back(d)
     return q
+
+
+def native_chord_backend():
+    return isinstance(_CHORD_BACKEND, str)
+
+
+def chords_native(q, wc, profile="krumhansl", given_tonic=None, analyse_key=True):
+    """rgm_rule_chords on the current stream: integer roll q (N,128,T) uint8 on the device, wc columns per window -> device tensors
+    chords (N,W) int64, roots (N,W) int32 (-1: silent window), key (N) int32 (12 * mode + tonic, -1: none), coefficient (N) float64.
+    given_tonic: None or 0..11 (one tonic for the batch); analyse_key=False needs it."""
+    _rgm.require_cuda(q)
+    if q.dim() != 3 or q.shape[1] != 128 or q.dtype != torch.uint8:
+        raise ValueError(f"integer roll must be (N, 128, T) uint8, got {tuple(q.shape)} {q.dtype}")
+    wc = int(wc)
+    if not 1 <= wc <= CHORD_MAX_WINDOW:
+        raise ValueError(f"chord window of {wc} columns: must be in 1 .. {CHORD_MAX_WINDOW}")
+    if given_tonic is None and not analyse_key:
+        raise ValueError("without key analysis a given tonic is needed")
+    prof = chord_profile(profile)
+    N, _, T = q.shape
+    W, dev = T // wc, q.device
+    if (dev, profile) not in _PROFILE_DEV:
+        _PROFILE_DEV[(dev, profile)] = torch.tensor(prof, dtype=torch.float64, device=dev)
+    given = None if given_tonic is None else torch.full((N,), int(given_tonic) % 12, dtype=torch.int32, device=dev)
+    chords = torch.empty((N, W), dtype=torch.int64, device=dev)
+    roots = torch.empty((N, W), dtype=torch.int32, device=dev)
+    key = torch.empty((N,), dtype=torch.int32, device=dev)
+    coef = torch.empty((N,), dtype=torch.float64, device=dev)
+    ws = torch.empty((N * (W + 1) * 12,), dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        _rgm.check(_rgm.lib.rgm_rule_chords(_rgm.ptr(q.contiguous()), N, T, wc, _rgm.ptr(_PROFILE_DEV[(dev, profile)]), _rgm.ptr(given),
+                                            int(bool(analyse_key)), _rgm.ptr(chords), _rgm.ptr(roots), _rgm.ptr(key), _rgm.ptr(coef),
+                                            _rgm.ptr(ws), ws.numel() * 4, _rgm.current_stream()))
+    return chords, roots, key, coef
+
+
+def _get_chords_native(piano_roll_batch, given_key, fs, window_size, return_key):
+    """get_chords under the "native" backend: the preamble's writes into the caller's roll, then the analyser on the same stream.  The
+    chords stay on the roll's device; only return_key reads back (the keys and coefficients are Python lists, like the host path's)."""
+    wc = chord_window_columns(fs, window_size)                      # ValueError before any launch
+    tonic = None if given_key is None else parse_key(given_key)
+    q = chord_quantise(piano_roll_batch)
+    chords, _, key, coef = chords_native(q, wc, _CHORD_PROFILE, tonic, analyse_key=return_key or tonic is None)
+    chords = chords.to(piano_roll_batch.device)
+    if chords.shape[0] == 1:
+        chords = chords.squeeze(0)
+    if return_key:
+        return chords, [key_class(k) for k in key.tolist()], coef.tolist()
+    return chords
 
 
 def _chord_job(args):
@@ -193,6 +300,19 @@ class ChordFuture:
         return _pack_chords(self._fut.result(), self._return_key)
 
 
+class _ReadyChords(ChordFuture):
+    """the "native" backend's answer: device tensors behind the kernels already enqueued on the caller's stream -- nothing to wait for"""
+
+    def __init__(self, value):
+        self._value = value
+
+    def done(self):
+        return True
+
+    def result(self):
+        return self._value
+
+
 def get_chords_async(piano_roll_batch, given_key=None, fs=100, window_size=1.28, return_key=False):
     """get_chords without the wait: (N,C,128,T) DEVICE roll -> ChordFuture.  The roll is read (and, like get_chords, written: mask +
     background snap) by a kernel on the current stream; the caller may go on using it on that stream at once."""
@@ -201,6 +321,8 @@ def get_chords_async(piano_roll_batch, given_key=None, fs=100, window_size=1.28,
         raise ImportError("chord rules need a host analyser (the reference's is music21-based and not vendored): "
                           "music_rule_guidance.music_rules.register_chord_backend(piano_roll_to_chords)")
     _rgm.require_cuda(piano_roll_batch)
+    if native_chord_backend():                                            # no pinned copy, no side stream, no driver thread
+        return _ReadyChords(_get_chords_native(piano_roll_batch, given_key, fs, window_size, return_key))
     q = chord_quantise(piano_roll_batch)                                  # (N,128,T) uint8, current stream
     dev = q.device
     cur = torch.cuda.current_stream(dev)
@@ -234,6 +356,8 @@ def get_chords(piano_roll_batch, given_key=None, fs=100, window_size=1.28, retur
     if _CHORD_BACKEND is None:
         raise ImportError("chord rules need a host analyser (the reference's is music21-based and not vendored): "
                           "music_rule_guidance.music_rules.register_chord_backend(piano_roll_to_chords)")
+    if native_chord_backend():
+        return _get_chords_native(piano_roll_batch, given_key, fs, window_size, return_key)
     rolls = chord_quantise(piano_roll_batch).cpu().numpy().astype(np.intc)
     kw = dict(given_key=given_key, fs=fs, window_size=window_size, return_key=return_key)
     return _pack_chords(_run_chord_jobs([(_CHORD_BACKEND, rolls[i], kw) for i in range(rolls.shape[0])]), return_key)

@@ -9,14 +9,16 @@ events at equal ticks, channels, track layout, delta ticks -- is pinned to what 
 mido (tests/golden/midi_writer.npz, tests/test_host_logic.py); only mido's byte serialisation of those messages is this module's own,
 following the SMF 1.0 specification (format 1, 220 ticks per quarter note at 120 bpm -- pretty_midi's defaults).  Chord analysis
 (music21) stays a host plug-in: music_rules.register_chord_backend (blocking get_chords, or get_chords_async beside the GPU in the
-samplers' search step).  Host-side I/O only -- nothing here is on the sampling hot path.
+samplers' search step).  piano_roll_to_chords_native at the end is such a plug-in in numpy: the host partner of the device analyser
+(csrc/chords.hip), following the same written definition (docs/rounds/chords.md), not music21's -- agreement with music21 has not been
+measured.  Host-side I/O only -- nothing here is on the sampling hot path.
 """
 import math
 import struct
 
 import numpy as np
 
-from .music_rules import MAX_PIANO, MIN_PIANO
+from .music_rules import (CHORD_DEGREES, MAX_PIANO, MIN_PIANO, chord_profile, chord_window_columns, key_class, parse_key)
 
 RESOLUTION = 220            # ticks per quarter note
 TEMPO_US = 500000           # 120 bpm
@@ -343,3 +345,109 @@ def midi_to_full_piano_roll(pm, fs=100):
                 else:
                     roll[2, MIN_PIANO:MAX_PIANO + 1, t] = quantize_pedal(cc.value)
     return roll.astype(np.float32)
+
+
+# ---- the native chord and key analyser on the host (docs/rounds/chords.md).  Same definition and the same IEEE operations in the
+# same order as csrc/chords.hip, so the two agree bit for bit; registered like any analyser (register_chord_backend(
+# piano_roll_to_chords_native)) it runs through the worker pool and is the A/B partner of register_chord_backend("native").
+ROMAN = ("", "I", "II", "III", "IV", "V", "VI", "VII")
+
+
+def _native_key(D, prof):
+    """pitch-class durations D (12 ints) -> (key number 12 * mode + tonic or -1, Pearson r of the key).  Plain Python floats, sums in
+    class order: what the kernel computes with FMA contraction off."""
+    sx = 0.0
+    for c in range(12):
+        sx += D[c]
+    mx = sx / 12.0
+    sxx = 0.0
+    for c in range(12):
+        sxx += (D[c] - mx) * (D[c] - mx)
+    if sxx == 0.0:
+        return -1, 0.0
+    key, best = -1, 0.0
+    for mode in (0, 1):
+        P = prof[mode]
+        for tonic in range(12):
+            sy = 0.0
+            for c in range(12):
+                sy += P[(c - tonic) % 12]
+            my = sy / 12.0
+            sxy = syy = 0.0
+            for c in range(12):
+                dx, dy = D[c] - mx, P[(c - tonic) % 12] - my
+                sxy += dx * dy
+                syy += dy * dy
+            r = sxy / math.sqrt(sxx * syy)
+            if key < 0 or r > best:                       # the first maximum
+                key, best = 12 * mode + tonic, r
+    return key, best
+
+
+def _native_root(pitches):
+    """sounding pitches of a slice (ascending) -> root pitch class"""
+    S = {int(p) % 12 for p in pitches}
+    bass = int(pitches[0]) % 12
+    root, best = bass, -1
+    for k in range(12):
+        r = (bass + k) % 12
+        if r not in S:
+            continue
+        score = (8 * ((r + 7) % 12 in S) + 4 * ((r + 4) % 12 in S or (r + 3) % 12 in S) + 3 * ((r + 6) % 12 in S)
+                 + 2 * ((r + 10) % 12 in S or (r + 11) % 12 in S))
+        if score > best:
+            root, best = r, score
+    return root
+
+
+def native_roots(act, wc):
+    """act (88, T) bool, pitches 21..108 -> root pitch class per whole window of wc columns (-1: no sounding column): the longest run of
+    columns with one non-empty pitch set inside the window, the earliest among equals."""
+    W = act.shape[1] // wc
+    roots = np.full(W, -1, dtype=np.int64)
+    if W == 0:
+        return roots
+    cols = np.packbits(act[:, :W * wc], axis=0)                             # (11, W wc): one key per column
+    start = np.ones(W * wc, dtype=bool)
+    start[1:] = (cols[:, 1:] != cols[:, :-1]).any(axis=0)
+    start[::wc] = True                                                      # runs are cut at window boundaries
+    idx = np.nonzero(start)[0]
+    length = np.diff(np.append(idx, W * wc))
+    keep = cols[:, idx].any(axis=0)                                         # silent slices are not chords
+    idx, length = idx[keep], length[keep]
+    order = np.lexsort((idx, -length))                                      # longest first, earliest among equals
+    win, first = np.unique(idx[order] // wc, return_index=True)
+    for w, t in zip(win, idx[order][first]):
+        roots[w] = _native_root(np.nonzero(act[:, t])[0] + MIN_PIANO)
+    return roots
+
+
+def piano_roll_to_chords_native(piano_roll_excerpt, given_key=None, return_key=False, tagging_func=None, fs=100., window_size=1.28,
+                                profile="krumhansl"):
+    """The reference's per-excerpt analyser interface (piano_roll_to_chord.py:307-359) over the native definition: (128, T) integer roll
+    -> {"chords": int64 array (T // (window_size fs),), ["key": KEY_DICT class, "correlationCoefficient": float]}.  With given_key and not
+    return_key the key is not analysed; otherwise it is, an excerpt without a key (silence, flat pitch-class profile) answers zeros,
+    "no key" and 0.0, and the degrees use the given tonic when there is one.  tagging_func (default: the degree numbers themselves)
+    is called with the degree's Roman numeral ("" for a silent window)."""
+    wc = chord_window_columns(fs, window_size)
+    prof = chord_profile(profile)
+    tonic = None if given_key is None else parse_key(given_key)
+    roll = np.asarray(piano_roll_excerpt)
+    if roll.ndim != 2 or roll.shape[0] != 128:
+        raise ValueError(f"piano roll excerpt must be (128, T), got {roll.shape}")
+    act = roll[MIN_PIANO:MAX_PIANO + 1] > 0
+    W = act.shape[1] // wc
+    out = {}
+    if tonic is None or return_key:
+        per_pitch = act.sum(axis=1)
+        key, coef = _native_key([int(per_pitch[(c - MIN_PIANO) % 12::12].sum()) for c in range(12)], prof)
+        out = {"key": key_class(key), "correlationCoefficient": coef}
+        if key < 0:
+            return dict(out, chords=np.zeros(W, dtype=np.int64))
+        if tonic is None:
+            tonic = key % 12
+    roots = native_roots(act, wc)
+    chords = np.array([0 if r < 0 else CHORD_DEGREES[(r - tonic) % 12] for r in roots], dtype=np.int64)
+    if tagging_func is not None:
+        chords = np.array([tagging_func(ROMAN[d]) for d in chords], dtype=np.int64)
+    return dict(out, chords=chords)

@@ -43,13 +43,18 @@ DROPPED_RULES = []    # what setup_chord_backend removed under --skip_chord_rule
 
 def setup_chord_backend(args, config):
     """Chord rules (`chord_progression*`) need a host analyser with the signature of the reference's piano_roll_to_chords
-    (music21; not installable here).  --chord_backend module:function registers one (music_rules.register_chord_backend).
+    (music21; not installable here).  --chord_backend module:function registers one (music_rules.register_chord_backend);
+    --chord_backend native selects the device analyser instead (its own definition, docs/rounds/chords.md; --chord_profile picks its
+    key profiles).
     Without one a config that asks for chord conditioning is an ERROR -- a run that silently lacks the requested rule would write
     tables that look like a fully conditioned one.  The explicit opt-in `--skip_chord_rules True` removes the chord entries from
     target_rules, from the SCG weights and from the cond_fn lists instead; what was removed is logged, recorded in
     run_metadata.json and marked in the output directory name (`_nochord`)."""
     from music_rule_guidance import music_rules
     del DROPPED_RULES[:]
+    if getattr(args, "chord_backend", "") == "native":     # no colon: cannot collide with module:function
+        music_rules.register_chord_backend("native", profile=getattr(args, "chord_profile", "krumhansl"))
+        return config
     if getattr(args, "chord_backend", ""):
         import importlib
         mod, _, fn = args.chord_backend.partition(":")
@@ -101,6 +106,8 @@ def write_run_metadata(save_dir, args, extra=None):
             "targets_npz": getattr(args, "targets_npz", "") or None}
     from guided_diffusion.dit import long_backward
     meta["sampler"] = sampler_metadata(args)
+    meta["chord_backend"] = getattr(args, "chord_backend", "") or None
+    meta["chord_profile"] = getattr(args, "chord_profile", "krumhansl") if meta["chord_backend"] == "native" else None
     meta["long_backward"] = bool(long_backward())     # RGM_LONG_BACKWARD / set_long_backward: guidance beyond 256 / 288 tokens was allowed
     meta.update(extra or {})
     with open(os.path.join(save_dir, "run_metadata.json"), "w") as f:
@@ -393,8 +400,8 @@ def create_argparser():
 
 
 def add_sampler_arguments(parser):
-    """--sampler and the DPM-Solver++ options: one group for sample_rule.py and edit.py, with the choices and help texts that the
-    defaults dictionary of create_argparser (the reference's flags) cannot carry."""
+    """--sampler and the DPM-Solver++ options (and --chord_profile of the native chord analyser): the groups sample_rule.py and edit.py
+    share, with the choices and help texts that the defaults dictionary of create_argparser (the reference's flags) cannot carry."""
     g = parser.add_argument_group("sampler")
     g.add_argument("--sampler", default="config", choices=["config", "dpmpp"],
                    help="'config': the YAML's chain (DDPM, or DDIM with eta = 1 on sampling.timestep_respacing); 'dpmpp': DPM-Solver++(2M) "
@@ -403,6 +410,9 @@ def add_sampler_arguments(parser):
     g.add_argument("--dpmpp_order", type=int, default=2, choices=[1, 2], help="2: the multistep solver; 1: first order throughout")
     g.add_argument("--dpmpp_eta", type=float, default=1.0, choices=[0.0, 1.0],
                    help="1: the SDE form (stochastic; what SCG needs to have candidates); 0: the probability-flow ODE")
+    g = parser.add_argument_group("chord analyser")
+    g.add_argument("--chord_profile", default="krumhansl", choices=["krumhansl", "aarden"],
+                   help="key profiles of --chord_backend native (Krumhansl-Kessler or Aarden-Essen)")
     return parser
 
 

@@ -371,6 +371,28 @@ int rgm_rule_chord_quantise(float* roll, uint8_t* out, int N, int C, int T, void
  * ws: N * (T / Wc + 1) * 12 int32.  Two launches, no atomics: bitwise repeatable, a sample's answer independent of N and its row. */
 int rgm_rule_chords(const uint8_t* q, int N, int T, int Wc, const double* profile, const int32_t* given_tonic, int analyse_key,
                     int64_t* chords, int32_t* roots, int32_t* key, double* coef, void* ws, size_t ws_bytes, void* stream);
+/* mgeval's note statistics on the device                music_evaluation/mgeval/core.py:32-412 (class metrics), over the object of
+ * music_rule_guidance/piano_roll_to_chord.py:167-275 (piano_roll_to_pretty_midi) and the fork's pretty_midi/instrument.py:69-207
+ * (get_piano_roll), :301-340 (get_pitch_class_transition_matrix), :242-259 (get_end_time).  The values are the reference's for the
+ * in-memory object at fs = 100 (tests/golden/notes.npz); the full definition and its quirks are in docs/rounds/notes.md.
+ * roll: uint8 cells 0..127, read only, cell (n, c, p, t) at roll + n stride_n + c stride_c + p stride_p + t stride_t (bytes): a
+ *   channel-first (N,C,128,T) roll and the (N,128,T,C) tensor of decode_sample_for_midi are both read in place.  C = 1 [velocity],
+ *   2 [velocity | pedal], 3 [velocity | onset | pedal]; 1 <= T <= 32768.  first_column_onsets (C = 3): the onset channel counts as 127
+ *   in column 0 of every row whose raw velocity there is not 0 (guided_diffusion/midi_util.py:81-85).
+ * out_int (N,148) int64: notes n, total_used_pitch, pitch_range, mean_note_velocity (sum // n), pitch_class_transition_matrix (12 x 12,
+ *   normalize = 0).  out_real (N,16) float64: end_time, avg_IOI, mean_note_duration, note_density (n / end_time), the 12 values of
+ *   total_pitch_class_histogram.  NaN where mgeval answers NaN (avg_IOI for n < 2, the histogram of an empty rebuilt roll).
+ * ws: rgm_note_stats_workspace(N, T) bytes (0 for sizes out of range), 8-byte aligned.  Three launches on `stream`, no host sync, no
+ * floating-point atomics: bitwise repeatable, a sample's answer independent of N and its row. */
+size_t rgm_note_stats_workspace(int N, int T);
+int rgm_note_stats(const uint8_t* roll, long long stride_n, long long stride_c, long long stride_p, long long stride_t, int N, int C,
+                   int T, int first_column_onsets, int64_t* out_int, double* out_real, void* ws, size_t ws_bytes, void* stream);
+/* Float roll (N,C,128,T) in [-1, 1] -> the uint8 roll rgm_note_stats reads: (uint8) clamp((x + 1) * 63.5 + 2^-10, 0, 127), the
+ * quantiser of decode_sample_for_midi (midi_util.py:61) with a bias and WITHOUT its background threshold (:60): it inverts
+ * u8 / 63.5 - 1, on which scripts/sample_rule.py reports rules, for all 128 levels.  Plain truncation of that round trip loses levels
+ * 1..4, 9, 10, 18..21; a threshold at -0.95 would lose 1..3 (3 / 63.5 - 1 = -0.9528).  A caller who wants the decode's threshold
+ * on a continuous roll applies it first (docs/rounds/notes.md). */
+int rgm_roll_to_u8(const float* roll, uint8_t* out, int N, int C, int T, void* stream);
 /* torch.bucketize(v, bounds) as used by note_density_class (:86-94): out int64. */
 int rgm_bucketize(const float* v, const float* bounds, int nb, int64_t* out, int n, void* stream);
 /* mse_loss_mean / zero_one_loss_mean (rule_maps.py:17-22) over the last dim: a,b (rows,K) -> out (rows). */

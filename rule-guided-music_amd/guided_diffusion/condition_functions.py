@@ -147,7 +147,7 @@ def _rule_x0_vag(roll, rule, name, scale):
             _rgm.check(_rgm.lib.rgm_rule_pitch_hist_vag(_rgm.ptr(roll), _rgm.ptr(tgt), float(scale), None, _rgm.ptr(logp),
                                                         _rgm.ptr(d_roll), _rgm.ptr(scratch), N, Cc, T, _rgm.current_stream()))
         return logp, d_roll
-    if base in (music_rules.note_density, music_rules.note_density_class, music_rules.get_chords):
+    if base in (music_rules.note_density, music_rules.note_density_class, music_rules.get_chords, music_rules.note_stat_rule):
         # counting behind hard thresholds: the reference's autograd returns an all-zero gradient for these too
         # (every element of the roll is overwritten by a constant before it is summed, music_rules.py:66-70)
         return _mse_logp(fn(roll).reshape(N, -1).float(), rule.to(roll.device).reshape(N, -1)) * scale, None

@@ -1422,7 +1422,9 @@ def _extract_rule(rule_name, pred_xstart):
 
 # rules whose in-place writes into the roll (piano_like mask, < -0.95 background snap) are a subset of the chord preamble's own: a chord
 # rule BEHIND them in the rule dict reads the same integer roll whether or not they ran first, so its analysis may start ahead of them
-_CHORD_NEUTRAL_RULES = ("pitch_hist", "note_density", "note_density_hr_1", "note_density_hr_2", "note_density_class", "note_density_pixel")
+_CHORD_NEUTRAL_RULES = ("pitch_hist", "note_density", "note_density_hr_1", "note_density_hr_2", "note_density_class", "note_density_pixel",
+                        "mg_used_pitch", "mg_pitch_range", "mg_avg_ioi", "mg_mean_velocity", "mg_mean_duration", "mg_notes_per_second",
+                        "mg_pitch_class_hist", "mg_transition")      # the mg_* rules write nothing into the roll
 CHORD_ASYNC = __import__("os").environ.get("RGM_CHORD_ASYNC", "1") != "0"       # 0: the reference's blocking order (A/B runs, tests)
 CHORD_CHUNKS = int(__import__("os").environ.get("RGM_CHORD_CHUNKS", "4"))      # decode chunks of a search step when a chord rule is scored
 

@@ -9,6 +9,8 @@ Semantics kept from the reference, including the surprising ones:
 CPU tensors are accepted (the CLI evaluates final rolls from numpy): they are staged to the HIP device,
 processed there, and the in-place writes are copied back -- the computation never runs on the CPU.
 """
+import ctypes
+
 import numpy as np
 import torch
 
@@ -361,3 +363,108 @@ def get_chords(piano_roll_batch, given_key=None, fs=100, window_size=1.28, retur
     rolls = chord_quantise(piano_roll_batch).cpu().numpy().astype(np.intc)
     kw = dict(given_key=given_key, fs=fs, window_size=window_size, return_key=return_key)
     return _pack_chords(_run_chord_jobs([(_CHORD_BACKEND, rolls[i], kw) for i in range(rolls.shape[0])]), return_key)
+
+
+# ---- mgeval's note statistics (docs/rounds/notes.md): what the reference's music_evaluation/mgeval/core.py `metrics` returns for the
+# object its piano_roll_to_pretty_midi builds from a roll, on the device (csrc/notes.hip).  The host partner in numpy is
+# piano_roll_to_chord.piano_roll_note_stats; both are pinned to the reference by tests/golden/notes.npz.
+NOTE_STATS_FS = 100
+NOTE_STATS_MAX_T = 32768
+NOTE_STATS_INT = ("n_notes", "total_used_pitch", "pitch_range", "mean_note_velocity")
+NOTE_STATS_REAL = ("end_time", "avg_IOI", "mean_note_duration", "note_density_mgeval")
+
+
+def roll_to_u8(piano_roll):
+    """float device roll (N, C, 128, T) in [-1, 1] -> a new uint8 roll: (x + 1) 63.5 + 2^-10, clamped to 0 .. 127 and truncated, so that a
+    uint8 roll sent through u8 / 63.5 - 1 comes back in all 128 levels.  decode_sample_for_midi's background threshold (<= -0.95 -> 0) is
+    NOT applied: it would take levels 1 .. 3 away; on a continuous roll apply it first if the decode's roll is wanted
+    (docs/rounds/notes.md).  The input is not written to."""
+    _rgm.require_cuda(piano_roll)
+    if piano_roll.dim() != 4 or piano_roll.shape[2] != 128:
+        raise ValueError(f"piano roll must be (N, C, 128, T), got {tuple(piano_roll.shape)}")
+    d = piano_roll.detach().to(torch.float32).contiguous()
+    N, Cc, _, T = d.shape
+    out = torch.empty(d.shape, dtype=torch.uint8, device=d.device)
+    with torch.cuda.device(d.device):
+        _rgm.check(_rgm.lib.rgm_roll_to_u8(_rgm.ptr(d), _rgm.ptr(out), N, Cc, T, _rgm.current_stream()))
+    return out
+
+
+def _note_stats_layout(roll):
+    """-> (N, C, T, byte strides of sample / channel / pitch / column) of a channel-first (N, C, 128, T) or channel-last (N, 128, T, C)
+    uint8 roll; a shape that reads both ways ((N, 3, 128, 3) cannot occur: 128 pitches) is taken channel-first."""
+    if roll.dim() == 3 and roll.shape[1] == 128:
+        roll = roll.unsqueeze(1)
+    if roll.dim() != 4:
+        raise ValueError(f"roll must be (N, C, 128, T) or (N, 128, T, C), got {tuple(roll.shape)}")
+    s = roll.stride()
+    if roll.shape[2] == 128 and roll.shape[1] in (1, 2, 3):
+        return roll, roll.shape[0], roll.shape[1], roll.shape[3], (s[0], s[1], s[2], s[3])
+    if roll.shape[1] == 128 and roll.shape[3] in (1, 2, 3):
+        return roll, roll.shape[0], roll.shape[3], roll.shape[2], (s[0], s[3], s[1], s[2])
+    raise ValueError(f"roll must be (N, C, 128, T) or (N, 128, T, C) with C in 1..3, got {tuple(roll.shape)}")
+
+
+def note_stats_raw(roll, first_column_onsets=False):
+    """uint8 device roll in either layout -> (out_int (N, 148) int64, out_real (N, 16) float64) of rgm_note_stats, read in place"""
+    _rgm.require_cuda(roll)
+    if roll.dtype != torch.uint8:
+        raise ValueError(f"note_stats_raw reads uint8 rolls, got {roll.dtype}")
+    roll, N, Cc, T, strides = _note_stats_layout(roll)
+    if not 1 <= T <= NOTE_STATS_MAX_T:
+        raise ValueError(f"note statistics take 1 .. {NOTE_STATS_MAX_T} columns, got {T}")
+    if N == 0 or min(strides) <= 0:
+        raise ValueError("note statistics need a non-empty roll with positive strides")
+    dev = roll.device
+    out_int = torch.empty((N, 148), dtype=torch.int64, device=dev)
+    out_real = torch.empty((N, 16), dtype=torch.float64, device=dev)
+    with torch.cuda.device(dev):
+        nbytes = _rgm.lib.rgm_note_stats_workspace(N, T)
+        ws = torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=dev)
+        _rgm.check(_rgm.lib.rgm_note_stats(ctypes.c_void_p(roll.data_ptr()), *[int(x) for x in strides], N, Cc, T, int(bool(first_column_onsets)),
+                                           _rgm.ptr(out_int), _rgm.ptr(out_real), _rgm.ptr(ws), ws.numel() * 8, _rgm.current_stream()))
+    return out_int, out_real
+
+
+def note_stats(roll, fs=100, first_column_onsets=False):
+    """mgeval's eight note statistics of a batch of rolls, on the device.  roll: a uint8 device tensor, channel-first (N, C, 128, T) or the
+    (N, 128, T, C) tensor of decode_sample_for_midi (read in place), or a float roll (N, C, 128, T) in [-1, 1], which goes through
+    roll_to_u8; C = 1 [velocity], 2 [velocity | pedal] or 3 [velocity | onset | pedal].  -> dict of device tensors with the reference's raw
+    values, NaN included: n_notes, total_used_pitch, pitch_range, mean_note_velocity (N,) int64; end_time, avg_IOI, mean_note_duration,
+    note_density_mgeval (N,) float64; total_pitch_class_histogram (N, 12) float64; pitch_class_transition_matrix (N, 12, 12) int64.
+    The roll is not written to.  fs must be 100: mgeval hard-codes get_piano_roll(fs=100)."""
+    if fs != NOTE_STATS_FS:
+        raise ValueError(f"note statistics are defined at fs = 100 (mgeval hard-codes get_piano_roll(fs=100)), got fs = {fs}")
+    if roll.is_floating_point():
+        roll = roll_to_u8(roll)
+    oi, orl = note_stats_raw(roll, first_column_onsets)
+    out = {k: oi[:, i] for i, k in enumerate(NOTE_STATS_INT)}
+    out.update({k: orl[:, i] for i, k in enumerate(NOTE_STATS_REAL)})
+    out["total_pitch_class_histogram"] = orl[:, 4:16]
+    out["pitch_class_transition_matrix"] = oi[:, 4:148].reshape(-1, 12, 12)
+    return out
+
+
+NOTE_STAT_RULES = {"mg_used_pitch": "total_used_pitch", "mg_pitch_range": "pitch_range", "mg_avg_ioi": "avg_IOI",
+                   "mg_mean_velocity": "mean_note_velocity", "mg_mean_duration": "mean_note_duration",
+                   "mg_notes_per_second": "note_density_mgeval", "mg_pitch_class_hist": "total_pitch_class_histogram",
+                   "mg_transition": "pitch_class_transition_matrix"}
+
+
+def note_stat_rule(piano_roll, stat="total_used_pitch"):
+    """FUNC_DICT entry of one statistic: float roll (N, C, 128, T) -> (N, K) float32 on the roll's device, K = 1, 12
+    (total_pitch_class_histogram) or 144 (the transition matrix divided by its sum, mgeval's normalize = 2), NaN and inf replaced by 0 as
+    music_evaluator.delete_nan does; batch size 1 squeezes the batch dimension like the other rules.  Nothing is written into the roll."""
+    if not piano_roll.is_cuda:
+        if not torch.cuda.is_available():
+            raise _rgm.RgmError("rule kernels need a HIP device (no CPU fallback in the product path)")
+        src = piano_roll.detach().to(torch.device("cuda", torch.cuda.current_device()))
+    else:
+        src = piano_roll
+    v = note_stats(src)[stat]
+    N = v.shape[0]
+    v = v.reshape(N, -1).to(torch.float64)
+    if stat == "pitch_class_transition_matrix":
+        v = v / v.sum(dim=1, keepdim=True)
+    out = torch.nan_to_num(v, nan=0.0, posinf=0.0, neginf=0.0).to(torch.float32).to(piano_roll.device)
+    return out.squeeze(0) if N == 1 else out

@@ -451,3 +451,99 @@ def piano_roll_to_chords_native(piano_roll_excerpt, given_key=None, return_key=F
     if tagging_func is not None:
         chords = np.array([tagging_func(ROMAN[d]) for d in chords], dtype=np.int64)
     return dict(out, chords=chords)
+
+
+# ---- mgeval's note statistics on the host (docs/rounds/notes.md): what the reference's music_evaluation/mgeval/core.py `metrics`
+# returns for the object its piano_roll_to_pretty_midi (:167-275) builds from a roll, written from the definition -- a note list, the
+# rebuilt roll of the fork's get_piano_roll(fs=100), the pair matrix -- without a MIDI object.  Pinned to the reference by
+# tests/golden/notes.npz; the A/B partner of the device analyser (csrc/notes.hip, music_rules.note_stats), which never builds a note list.
+NOTE_STATS_FS = 100
+
+
+def _col(k):
+    """the column the fork's get_piano_roll gives the time k / 100: int((k / 100) * 100) in float64, k or k - 1"""
+    return int((k / 100) * 100)
+
+
+def piano_roll_note_stats(full_roll, fs=100, first_column_onsets=False):
+    """(128, T) or (C, 128, T) integer roll, C = 1 [velocity], 2 [velocity | pedal] or 3 [velocity | onset | pedal] -> dict of the
+    eight statistics plus n_notes and end_time (numpy scalars / arrays, NaN where mgeval answers NaN).  The input is not written to.
+    first_column_onsets: the onset channel counts as 127 in column 0 of every row that sounds there (what save_piano_roll_midi does
+    before it writes a file)."""
+    if fs != NOTE_STATS_FS:
+        raise ValueError(f"note statistics are defined at fs = 100 (mgeval hard-codes get_piano_roll(fs=100)), got fs = {fs}")
+    roll = np.array(full_roll, dtype=np.int64)                  # a copy: the reference's function writes into its input, this one does not
+    if roll.ndim == 2:
+        roll = roll[None]
+    if roll.ndim != 3 or roll.shape[0] not in (1, 2, 3) or roll.shape[1] != 128 or roll.shape[2] < 1:
+        raise ValueError(f"roll must be (128, T) or (C, 128, T) with C in 1..3 and T >= 1, got {np.shape(full_roll)}")
+    C, _, T = roll.shape
+    vel = roll[0]
+    onset = None
+    if C == 3:
+        onset = roll[1]
+        if first_column_onsets:
+            onset[vel[:, 0] != 0, 0] = 127
+        onset = onset >= 64
+    vel = np.where(vel > vel[:MIN_PIANO].max(), vel, 0)
+    # notes (pitch, start column, end column, velocity)
+    notes = []
+    for p in np.nonzero(vel.any(axis=1))[0]:
+        a = np.zeros(T + 2, dtype=np.int8)
+        a[1:-1] = vel[p] != 0
+        d = np.diff(a)
+        for s, e in zip(np.nonzero(d == 1)[0], np.nonzero(d == -1)[0]):
+            v = int(vel[p, s])
+            if onset is None:
+                notes.append((int(p), int(s), int(e), v))
+                continue
+            ons = s + np.nonzero(onset[p, s:e + 1])[0]           # the slice stops at T - 1
+            for o, nxt in zip(ons, list(ons[1:]) + [e]):
+                notes.append((int(p), int(o), int(nxt), v))
+    # pedal events (column, value)
+    events = []
+    if C >= 2:
+        ped = roll[C - 1]
+        ped = np.where(ped >= 4, ped, 0)[MIN_PIANO:MAX_PIANO + 1].sum(axis=0) // (MAX_PIANO - MIN_PIANO + 1)
+        events = [(int(t), 0 if ped[t] < 16 else (127 if ped[t] > 112 else int(ped[t]))) for t in np.nonzero(ped)[0]]
+    n = len(notes)
+    last = max([e for _, _, e, _ in notes] + [t for t, _ in events], default=0)
+    end_time = last / 100
+    out = {"n_notes": np.int64(n), "end_time": np.float64(end_time)}
+    # the rebuilt roll
+    W = _col(last) if n else 0
+    re = np.zeros((128, W), dtype=np.int64)
+    for p, s, e, v in notes:
+        re[p, _col(s):_col(e)] += v
+    down, press = False, 0
+    for t, v in events if n else []:
+        if v >= 64 and not down:
+            down, press = True, _col(t)
+        elif v < 64 and down:
+            down = False
+            re[:, press:_col(t)] = np.maximum.accumulate(re[:, press:_col(t)], axis=1)
+    rows = re.sum(axis=1)
+    used = np.nonzero(rows > 0)[0]
+    out["total_used_pitch"] = np.int64(len(used))
+    out["pitch_range"] = np.int64(used[-1] - used[0]) if len(used) else np.int64(0)
+    folded = np.array([rows[c::12].sum() for c in range(12)], dtype=np.float64)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        out["total_pitch_class_histogram"] = folded / folded.sum()
+    out["mean_note_velocity"] = np.int64(sum(v for _, _, _, v in notes) // n) if n else np.int64(0)
+    dur = 0.0
+    for _, s, e, _ in notes:
+        dur += e / 100 - s / 100
+    out["mean_note_duration"] = np.float64(dur / n) if n else np.float64(0.0)
+    out["note_density_mgeval"] = np.float64(n / end_time) if end_time > 0 else np.float64(0.0)
+    starts = sorted(s for _, s, _, _ in notes)
+    out["avg_IOI"] = np.float64((starts[-1] / 100 - starts[0] / 100) / (n - 1)) if n >= 2 else np.float64(np.nan)
+    M = np.zeros((12, 12), dtype=np.int64)
+    if n > 1:
+        pc = np.array([p % 12 for p, _, _, _ in notes])
+        st = np.array([s for _, s, _, _ in notes], dtype=np.float64) / 100
+        en = np.array([e for _, _, e, _ in notes], dtype=np.float64) / 100
+        for i0 in range(0, n, 1024):                                # ends in blocks: the pair matrix never holds more than 1024 n cells
+            src, dst = np.nonzero(np.abs(np.subtract.outer(en[i0:i0 + 1024], st)) < 0.05)
+            np.add.at(M, (pc[i0:i0 + 1024][src], pc[dst]), 1)
+    out["pitch_class_transition_matrix"] = M
+    return out

@@ -18,6 +18,9 @@ FUNC_DICT = {
     "note_density_pixel": partial(music_rules.note_density, interval=16),     # lower time resolution
     "chord_progression_pixel": partial(music_rules.get_chords, fs=12.5),
 }
+# mgeval's note statistics (docs/rounds/notes.md): mg_used_pitch, mg_pitch_range, mg_avg_ioi, mg_mean_velocity, mg_mean_duration,
+# mg_notes_per_second (N, 1), mg_pitch_class_hist (N, 12), mg_transition (N, 144)
+FUNC_DICT.update({name: partial(music_rules.note_stat_rule, stat=stat) for name, stat in music_rules.NOTE_STAT_RULES.items()})
 
 
 def _row_loss(gen_rule, y_, zero_one):
@@ -61,3 +64,4 @@ LOSS_DICT = {
     "note_density_pixel": mse_loss_mean,
     "chord_progression_pixel": zero_one_loss_mean,
 }
+LOSS_DICT.update({name: mse_loss_mean for name in music_rules.NOTE_STAT_RULES})

@@ -75,6 +75,9 @@ def _load():
         "rgm_rule_note_density": (C.c_int, [vp, vp, i32, i32, i32, i32, f32, vp]),
         "rgm_rule_chord_quantise": (C.c_int, [vp, vp, i32, i32, i32, vp]),
         "rgm_rule_chords": (C.c_int, [vp, i32, i32, i32, vp, vp, i32, vp, vp, vp, vp, vp, sz, vp]),
+        "rgm_note_stats_workspace": (sz, [i32, i32]),
+        "rgm_note_stats": (C.c_int, [vp] + [C.c_longlong] * 4 + [i32, i32, i32, i32, vp, vp, vp, sz, vp]),
+        "rgm_roll_to_u8": (C.c_int, [vp, vp, i32, i32, i32, vp]),
         "rgm_bucketize": (C.c_int, [vp, vp, i32, vp, i32, vp]),
         "rgm_row_loss": (C.c_int, [vp, vp, vp, i32, i32, i32, vp]),
         "rgm_collage_split": (C.c_int, [vp, vp, vp, i32, i32, i32, i32, i32, i32, vp]),

@@ -196,6 +196,7 @@ def main(argv=None):
             guidance_kwargs=config.guidance, scg_kwargs=vars(config.scg) if use_scg else None, edit_kwargs=edit_kwargs,
             t_end=config.sampling.t_end, record=args.record, progress=args.progress, **({} if start is None else {"noise": start}))
         sample = midi_util.decode_sample_for_midi(sample, embed_model=embed_model, scale_factor=args.scale_factor, threshold=-0.95)
+        note_cols = _sr.note_stats_columns(sample) if args.note_stats else {}                 # the whole saved roll, on the device
         arr = sample.cpu().numpy().transpose(0, 3, 1, 2)
         arr_gt = ((gt + 1) * 63.5).clamp(0, 127).to(th.uint8).cpu().numpy()
         if args.save_files and rank0:
@@ -207,13 +208,15 @@ def main(argv=None):
         results = midi_util.eval_rule_loss(generated, model_kwargs["rule"])
         for name, o in orig.items():
             results[name + ".orig_rule"] = [o.reshape(-1).cpu().tolist()] * len(results)
+        for name, col in note_cols.items():
+            results[name] = col
         all_results = pd.concat([all_results, results], ignore_index=True)
         if args.save_files and rank0:
             all_results.to_csv(os.path.join(save_dir, "results.csv"), index=False)
         count_samples += args.batch_size
 
     if args.save_files and rank0:
-        loss_cols = [c for c in all_results.columns if ".loss" in c]
+        loss_cols = _sr.summary_columns(all_results)
         stats = pd.DataFrame([{"Attr": c, "Mean": all_results[c].mean(), "Std": all_results[c].std()} for c in loss_cols],
                              columns=["Attr", "Mean", "Std"])
         stats.to_csv(os.path.join(save_dir, "summary.csv"))
@@ -223,7 +226,7 @@ def main(argv=None):
 
 
 def create_argparser():
-    parser = _sr.add_sampler_arguments(_sample_argparser())
+    parser = _sr.add_note_stats_arguments(_sr.add_sampler_arguments(_sample_argparser()))
     parser.add_argument("--allow_synthetic_source", default=False, type=lambda v: str(v).lower() in ("yes", "true", "t", "y", "1"),
                         help="edit.source 'dataset' needs the reference's data loader; True substitutes a seeded synthetic roll "
                              "(marked in the output directory name and run_metadata.json)")

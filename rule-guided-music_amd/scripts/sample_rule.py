@@ -27,7 +27,7 @@ import torch as th  # noqa: E402
 from guided_diffusion import dist_util, midi_util, logger  # noqa: E402
 from guided_diffusion.dit import DiT_models  # noqa: E402
 from guided_diffusion.script_util import (  # noqa: E402
-    NUM_CLASSES, model_and_diffusion_defaults, create_diffusion, add_dict_to_argparser, args_to_dict)
+    NUM_CLASSES, model_and_diffusion_defaults, create_diffusion, add_dict_to_argparser, args_to_dict, str2bool)
 from guided_diffusion.gaussian_diffusion import _extract_rule  # noqa: E402
 from guided_diffusion.condition_functions import model_fn, dc_model_fn, composite_nn_zt, composite_rule  # noqa: E402
 from load_utils import load_model  # noqa: E402
@@ -108,10 +108,32 @@ def write_run_metadata(save_dir, args, extra=None):
     meta["sampler"] = sampler_metadata(args)
     meta["chord_backend"] = getattr(args, "chord_backend", "") or None
     meta["chord_profile"] = getattr(args, "chord_profile", "krumhansl") if meta["chord_backend"] == "native" else None
+    meta["note_stats"] = bool(getattr(args, "note_stats", False))   # notes.* columns in results.csv (docs/rounds/notes.md)
     meta["long_backward"] = bool(long_backward())     # RGM_LONG_BACKWARD / set_long_backward: guidance beyond 256 / 288 tokens was allowed
     meta.update(extra or {})
     with open(os.path.join(save_dir, "run_metadata.json"), "w") as f:
         json.dump(meta, f, indent=1)
+
+
+NOTE_STATS_SCALARS = ("n_notes", "end_time", "total_used_pitch", "pitch_range", "avg_IOI", "mean_note_velocity", "mean_note_duration",
+                      "note_density_mgeval")
+
+
+def note_stats_columns(sample_u8, t0=None, t1=None):
+    """--note_stats: mgeval's note statistics (docs/rounds/notes.md) of the uint8 rolls decode_sample_for_midi returns, (B, 128, T, 3) on
+    the device, read there in place, as the saved MIDI files hold them (first-column onsets set) -> {"notes.<statistic>": one value per
+    sample}: numbers for the scalar statistics, lists for the histogram (12) and the transition matrix (12 x 12)."""
+    from music_rule_guidance import music_rules
+    st = music_rules.note_stats(sample_u8 if t0 is None else sample_u8[:, :, t0:t1], first_column_onsets=True)
+    cols = {"notes." + k: st[k].cpu().tolist() for k in NOTE_STATS_SCALARS}
+    cols["notes.total_pitch_class_histogram"] = st["total_pitch_class_histogram"].cpu().tolist()
+    cols["notes.pitch_class_transition_matrix"] = st["pitch_class_transition_matrix"].cpu().tolist()
+    return cols
+
+
+def summary_columns(all_results):
+    """the columns summary.csv averages: the rule losses, and under --note_stats the scalar note statistics (NaN skipped)"""
+    return [c for c in all_results.columns if ".loss" in c] + ["notes." + k for k in NOTE_STATS_SCALARS if "notes." + k in all_results.columns]
 
 
 def choose_sampler(args, config):
@@ -303,7 +325,7 @@ def build_pipeline(args, config, device):
 
 
 def main(argv=None):
-    args = add_sampler_arguments(create_argparser()).parse_args(argv)
+    args = add_note_stats_arguments(add_sampler_arguments(create_argparser())).parse_args(argv)
     args.dir = output_dir_for(args.config_path, args.class_label)
     from rgm import native as _native
     _native.set_gemm_precision(args.gemm_precision)      # "bf16x3_presplit" / "bf16x3" (fast, fp32-grade) or "fp32" (exact fp32 MFMA)
@@ -356,19 +378,22 @@ def main(argv=None):
             with _native.gemm_precision_scope("fp32" if midi_util.FINAL_DECODE_EXACT else None):   # the final decode's own arithmetic
                 KEEP_FLOAT_ROLLS.append(_decode(sample, embed_model, scale_factor=args.scale_factor).float().cpu().numpy())
         sample = midi_util.decode_sample_for_midi(sample, embed_model=embed_model, scale_factor=args.scale_factor, threshold=-0.95)
+        note_cols = note_stats_columns(sample) if args.note_stats else {}                  # on the device, before the roll leaves it
         arr = sample.cpu().numpy().transpose(0, 3, 1, 2)                                   # (B, 3, 128, T) uint8
         if args.save_files and rank0:
             midi_util.save_piano_roll_midi(arr, save_dir, args.fs, y=classes.cpu().numpy() if classes is not None else None,
                                            save_ind=count_samples)
         generated = th.from_numpy(arr.astype(np.float32)) / 63.5 - 1
         results = midi_util.eval_rule_loss(generated, model_kwargs["rule"])
+        for name, col in note_cols.items():
+            results[name] = col
         all_results = pd.concat([all_results, results], ignore_index=True)
         if args.save_files and rank0:
             all_results.to_csv(os.path.join(save_dir, "results.csv"), index=False)
         count_samples += args.batch_size
 
     if args.save_files and rank0:
-        loss_cols = [c for c in all_results.columns if ".loss" in c]
+        loss_cols = summary_columns(all_results)
         stats = pd.DataFrame([{"Attr": c, "Mean": all_results[c].mean(), "Std": all_results[c].std()} for c in loss_cols],
                              columns=["Attr", "Mean", "Std"])
         stats.to_csv(os.path.join(save_dir, "summary.csv"))
@@ -413,6 +438,17 @@ def add_sampler_arguments(parser):
     g = parser.add_argument_group("chord analyser")
     g.add_argument("--chord_profile", default="krumhansl", choices=["krumhansl", "aarden"],
                    help="key profiles of --chord_backend native (Krumhansl-Kessler or Aarden-Essen)")
+    return parser
+
+
+def add_note_stats_arguments(parser):
+    """--note_stats: the opt-in notes.* report columns of sample_rule.py and edit.py (kept out of create_argparser's defaults, which
+    mirror the reference's flags)."""
+    g = parser.add_argument_group("note statistics")
+    g.add_argument("--note_stats", default=False, type=str2bool,
+                   help="True: mgeval's note statistics of every saved roll (used pitches, pitch range, average IOI, pitch-class histogram, "
+                        "mean velocity / duration, notes per second, transition matrix) as notes.* columns of results.csv, their means in "
+                        "summary.csv; computed on the device (docs/rounds/notes.md)")
     return parser
 
 

@@ -393,6 +393,33 @@ int rgm_note_stats(const uint8_t* roll, long long stride_n, long long stride_c, 
  * 1..4, 9, 10, 18..21; a threshold at -0.95 would lose 1..3 (3 / 63.5 - 1 = -0.9528).  A caller who wants the decode's threshold
  * on a continuous roll applies it first (docs/rounds/notes.md). */
 int rgm_roll_to_u8(const float* roll, uint8_t* out, int N, int C, int T, void* stream);
+/* The set-level half of mgeval                           music_evaluation/music_evaluator.py:117-186, mgeval/utils.py (c_dist, kl_dist,
+ * overlap_area), csrc/sets.hip; definition, quirks and measurements in docs/rounds/sets.md.  Everything is float64 on `stream` in the
+ * caller's workspace (8-byte aligned), no host sync, no atomics, no FMA contraction; every sum has one owner and a fixed order and the
+ * chunking is a constant of the build, so a result depends on its inputs alone and repeats bit for bit.  Size errors return a status
+ * before any launch.
+ *
+ * rgm_set_distances: a (Na,d), b (Nb,d) row-major, 1 <= Na, Nb <= 32768, 1 <= d <= 144.  out[i][j] = sqrt(sum_k (a[i,k] - b[j,k])^2),
+ *   summed in k order; NaN and +-inf results are written as 0 (music_evaluator.delete_nan).  skip_diagonal (needs Na == Nb >= 2): a
+ *   row holds the Nb - 1 entries j != i in ascending j -- the leave-one-out loop after its transpose and reshape.
+ * rgm_kde_pdf: scipy.stats.gaussian_kde(data)(x) for one-dimensional data: h = sqrt(sum (y - mean)^2 / (n - 1)) n^(-1/5),
+ *   pdf(x) = sum_j exp(-((x - y_j) / h)^2 / 2) / (n h sqrt(2 pi)), (x - y) / h formed per pair.  1 <= n <= 2^24, 1 <= m <= 2^20; n < 2
+ *   or a zero variance writes NaN to every output (no status: the caller cannot know without a sync).  ws: rgm_kde_pdf_workspace(n, m).
+ * rgm_set_kl_oa: kl_dist(A, B, kl_points) and overlap_area(A, B) in one call.  KL = sum p log(p / q) (scipy.special.rel_entr's rules for
+ *   zeros) of pdf_A on linspace(min A, max A, kl_points) and pdf_B on linspace(min B, max B, kl_points) -- two different point sets, the
+ *   reference's definition -- each divided by its sum.  OA = the composite Simpson rule of min(pdf_A, pdf_B) on oa_panels + 1 equally
+ *   spaced points over [min(min A, min B), max(max A, max B)], in place of QUADPACK's adaptive rule.  linspace is lo + i (hi - lo) /
+ *   (points - 1) with the last point equal to hi.  2 <= nA, nB <= 2^24, 2 <= kl_points <= 4096, oa_panels even in 2 .. 65536 (the
+ *   Python surface defaults to 1000 and 16384).
+ *   out[8]: KL, OA, |OA(oa_panels) - OA(oa_panels / 2)| (NaN unless oa_panels is a multiple of 4), h_A, h_B, lo, hi, flag.  flag = 1 and
+ *   KL = OA = NaN where a variance is 0 (the reference raises LinAlgError there).  ws: rgm_set_kl_oa_workspace(...) bytes (0 for sizes out
+ *   of range): 16 (1 + chunks) (kl_points + oa_panels + 1) + 128, chunks = ceil(max(nA, nB) / 16384).  Four launches. */
+int rgm_set_distances(const double* a, int Na, const double* b, int Nb, int d, int skip_diagonal, double* out, void* stream);
+size_t rgm_kde_pdf_workspace(int n, int m);
+int rgm_kde_pdf(const double* data, int n, const double* x, int m, double* pdf, void* ws, size_t ws_bytes, void* stream);
+size_t rgm_set_kl_oa_workspace(int nA, int nB, int kl_points, int oa_panels);
+int rgm_set_kl_oa(const double* A, int nA, const double* B, int nB, int kl_points, int oa_panels, double* out, void* ws, size_t ws_bytes,
+                  void* stream);
 /* torch.bucketize(v, bounds) as used by note_density_class (:86-94): out int64. */
 int rgm_bucketize(const float* v, const float* bounds, int nb, int64_t* out, int n, void* stream);
 /* mse_loss_mean / zero_one_loss_mean (rule_maps.py:17-22) over the last dim: a,b (rows,K) -> out (rows). */

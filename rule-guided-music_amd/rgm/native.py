@@ -78,6 +78,11 @@ def _load():
         "rgm_note_stats_workspace": (sz, [i32, i32]),
         "rgm_note_stats": (C.c_int, [vp] + [C.c_longlong] * 4 + [i32, i32, i32, i32, vp, vp, vp, sz, vp]),
         "rgm_roll_to_u8": (C.c_int, [vp, vp, i32, i32, i32, vp]),
+        "rgm_set_distances": (C.c_int, [vp, i32, vp, i32, i32, i32, vp, vp]),
+        "rgm_kde_pdf_workspace": (sz, [i32, i32]),
+        "rgm_kde_pdf": (C.c_int, [vp, i32, vp, i32, vp, vp, sz, vp]),
+        "rgm_set_kl_oa_workspace": (sz, [i32, i32, i32, i32]),
+        "rgm_set_kl_oa": (C.c_int, [vp, i32, vp, i32, i32, i32, vp, vp, sz, vp]),
         "rgm_bucketize": (C.c_int, [vp, vp, i32, vp, i32, vp]),
         "rgm_row_loss": (C.c_int, [vp, vp, vp, i32, i32, i32, vp]),
         "rgm_collage_split": (C.c_int, [vp, vp, vp, i32, i32, i32, i32, i32, i32, vp]),

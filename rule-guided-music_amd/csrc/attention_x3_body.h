@@ -1,5 +1,5 @@
-// attention_x3_body.h -- the single-pass bf16x3 attention of attention_x3.hip (design notes there) as a device function: the one-launch
-// kernel wraps it, chain.hip runs it as a work item of the persistent DiT forward.
+// attention_x3_body.h -- the single-pass bf16x3 attention of attention_x3.hip (design notes there) as a device function:
+// rotary_attention_x3_kernel wraps it, one workgroup per (sample, head, query group).
 #pragma once
 #include <stdlib.h>
 #include "common.h"
@@ -45,11 +45,10 @@ __device__ float* g_attn_dump = nullptr;    // [grid][waves][ATTN_DUMP_ITEMS][64
 #endif
 
 // The single-pass kernel's body for workgroup `bidx` of the (sample, head, query group) grid; smem3 = the workgroup's dynamic LDS.
-// COH = 1 (chain.hip, out_split only): the output rows are stored device-coherent, 16 bytes per lane (lanes l / l + 32 pair their halves).
-template <int HD, int NKT, int COH = 0>
+template <int HD, int NKT>
 __device__ __forceinline__ void attn_x3_body(char* smem3, const float* __restrict__ qkv, float* __restrict__ o,
                                              const float* __restrict__ cos_tab, const float* __restrict__ sin_tab, int T, int heads,
-                                             int rot_half, float* __restrict__ lse, int out_split, int qgroups, const int bidx, const int tid_in = -1) {
+                                             int rot_half, float* __restrict__ lse, int out_split, int qgroups, const int bidx) {
   constexpr int KP = (HD + 15) / 16 * 16;   // padded contraction length of QK^T
   constexpr int KS = KP / 16;               // k16 steps of QK^T
   constexpr int DT = (HD + 31) / 32;        // 32-wide output-channel tiles
@@ -66,7 +65,7 @@ __device__ __forceinline__ void attn_x3_body(char* smem3, const float* __restric
   const int n = bh / heads, head = bh - n * heads;
   const int D = heads * HD, D3 = 3 * D;
   const float* base = qkv + (long long)n * T * D3 + head * HD;
-  const int tid = tid_in >= 0 ? tid_in : (int)threadIdx.x;
+  const int tid = threadIdx.x;
   const int R = 2 * rot_half;
   typedef split_t bf16x4 __attribute__((ext_vector_type(4)));
 
@@ -88,8 +87,8 @@ __device__ __forceinline__ void attn_x3_body(char* smem3, const float* __restric
   const int nthr = blockDim.x;
   constexpr int CPR = KP / 4;               // float4 chunks per padded K row
   // U chunks per thread and iteration, every load of the U (K, V and the rotary factors) requested before the first is used: with one
-  // chunk per iteration a 256-thread workgroup (chain.hip: nobody else on the CU) walked 20 dependent round trips -- 35 of the 52 us of a
-  // (sample, head) item (tools/chain_spans.py)
+  // chunk per iteration a 256-thread workgroup walked 20 dependent round trips -- 35 of the 52 us of a (sample, head) item, measured on a
+  // workgroup that had its CU to itself
   constexpr int U = 5;
   for (int c0 = tid; c0 < TP * CPR; c0 += U * nthr) {
     float4 kvs[U], vvs[U];
@@ -354,11 +353,8 @@ __device__ __forceinline__ void attn_x3_body(char* smem3, const float* __restric
               lo[0] = (split_t)(ov.x - (float)hi[0]); lo[1] = (split_t)(ov.y - (float)hi[1]);
               lo[2] = (split_t)(ov.z - (float)hi[2]); lo[3] = (split_t)(ov.w - (float)hi[3]);
               split_t* rp = reinterpret_cast<split_t*>(o + ((long long)n * T + q) * D);
-              if constexpr (COH) {   // lanes l (hh = 0: channels 8g .. +3) and l + 32 (hh = 1: +4 .. +7) hold one 8-aligned group (HD % 8 == 0)
-                store_split4_pair_sc1<32>(rp, head * HD + d, hi, lo);
-              } else {
-                store_split4_maybe_pair<32>(rp, head * HD + d, hi, lo);   // the same pairing, ordinary stores
-              }
+              // lanes l (hh = 0: channels 8g .. +3) and l + 32 (hh = 1: +4 .. +7) hold one 8-aligned group (HD % 8 == 0): 16 bytes per lane
+              store_split4_maybe_pair<32>(rp, head * HD + d, hi, lo);
             } else {
               *reinterpret_cast<float4*>(op + d) = ov;
             }

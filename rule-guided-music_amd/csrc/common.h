@@ -85,44 +85,11 @@ __device__ __forceinline__ void static_for(F&& f) {
 }
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
-// ---------------------------------------------------------------------------------------------
-// Device-coherent ("write-through", sc1) stores: what a workgroup of a persistent launch publishes for ANOTHER workgroup of the same
-// launch (chain.hip).  The bytes leave the XCD's L2 when vmcnt retires the store -- no cache write-back (an agent-scope release fence
-// writes the whole dirty L2 back: MI355X_MICROARCH.md "publish-large", 8.2 against 3.0 us per 64 KB), so the hand-off is
-//   sc1 stores -> s_waitcnt vmcnt(0) -> barrier -> relaxed agent-scope counter add      (producer)
-//   relaxed agent-scope poll -> agent-scope acquire fence (L1 invalidate) -> barrier -> plain loads / LDS-DMA   (consumer).
-// 16 bytes per lane: narrower sc1 stores are one fabric write each (a dwordx2 costs 2.7x per byte) -- 8-byte pieces of split rows are
-// paired over two lanes first (store_split4_pair_sc1).
-// ---------------------------------------------------------------------------------------------
-__device__ __forceinline__ void store16_sc1(void* p, const f32x4& v) {
-  // s_nop: a store of more than 8 bytes still reads its data registers for a wait state or two after issue, and the compiler's hazard
-  // recogniser does not see a store inside an asm statement -- without it the next VALU write of those registers corrupted the last
-  // four lanes of every 16 (found on the attention output: rows 12-15 / 28-31 of a query tile, run-to-run different).
-  // No "memory" clobber: a clobber pins every load behind the previous store (the row items of chain.hip walked one round trip per
-  // 16-byte chunk that way); volatile asm statements keep their order among themselves, and where an epilogue counts on the order of its
-  // LDS-DMA loads against these stores (gemm2_body.h staged_dma_res) it fences the loads with compiler barriers of its own.
-  asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" ::"v"(p), "v"(v));
-}
 typedef split_t split_x4 __attribute__((ext_vector_type(4)));
-// A lane holds 4 consecutive elements (columns col .. col + 3, col % 4 == 0) of a split row as hi / lo halves; its partner lane
-// (lane ^ XOR) holds the other 4 of the same 8-aligned group.  The lane with (col & 4) == 0 stores the 8 hi halves (16 bytes), the other
-// the 8 lo halves: two 16-byte coherent stores instead of four 8-byte ones.  Both lanes of a pair must call (shuffle inside).
-template <int XOR>
-__device__ __forceinline__ void store_split4_pair_sc1(split_t* rowp, int col, const split_x4& hi, const split_x4& lo) {
-  typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-  const bool even = (col & 4) == 0;
-  const u32x2 mine_hi = __builtin_bit_cast(u32x2, hi), mine_lo = __builtin_bit_cast(u32x2, lo);
-  const u32x2 send = even ? mine_lo : mine_hi;           // the even lane needs the partner's hi, the odd lane the partner's lo
-  u32x2 recv;
-  recv[0] = (unsigned)__shfl_xor((int)send[0], XOR, 64);
-  recv[1] = (unsigned)__shfl_xor((int)send[1], XOR, 64);
-  typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-  const u32x4 out = even ? u32x4{mine_hi[0], mine_hi[1], recv[0], recv[1]} : u32x4{recv[0], recv[1], mine_lo[0], mine_lo[1]};
-  split_t* dst = rowp + split_idx(col & ~7) + (even ? 0 : 32);
-  store16_sc1(dst, __builtin_bit_cast(f32x4, out));
-}
-
-// The same pairing for ordinary (non-coherent) stores, neighbouring lanes (lane ^ 1, exchanged with a DPP quad permute: no LDS traffic).
+// Split rows as 16-byte stores.  A lane holds 4 consecutive elements (columns col .. col + 3, col % 4 == 0) of a split row as hi / lo halves;
+// its partner lane (lane ^ XOR) holds the other 4 of the same 8-aligned group.  The lane with (col & 4) == 0 stores the 8 hi halves (16 bytes),
+// the other the 8 lo halves: two 16-byte stores instead of four 8-byte ones.  Neighbouring lanes (XOR = 1) exchange with a DPP quad permute:
+// no LDS traffic.
 // An 8-byte store costs an issue slot like a 16-byte one, and a write-bound epilogue is store-ISSUE-bound: the 256x256 tile's epilogue takes
 // 33.8 k cycles with split-row output as 2 x 8 bytes per lane against 25.5 k for the same bytes as fp32 rows (tools/gemm_stamp.py, SPLIT=1).
 // NT: non-temporal (the one-wave-per-SIMD kernels' 57-76 MB outputs).  Both lanes of a pair must call.
@@ -162,8 +129,9 @@ __device__ __forceinline__ void store_split4_maybe_pair(split_t* rowp, int col, 
   }
 }
 
-// 16-byte load from GLOBAL memory, said so: a pointer that reaches a device function through a descriptor in memory (chain.hip) is a
-// generic pointer to the compiler -- flat loads, which count on lgkmcnt as well and serialise against the LDS traffic around them
+// 16-, 8- and 4-byte loads from GLOBAL memory, said so (address space 1): where the compiler cannot prove that a pointer is global -- one
+// that reaches a device function through a struct in memory, for instance -- it is a generic pointer, and generic means flat loads, which
+// count on lgkmcnt as well as vmcnt and serialise against the LDS traffic around them
 __device__ __forceinline__ float4 ldg16(const float* q) {
   const f32x4 v = *(const __attribute__((address_space(1))) f32x4*)q;
   return make_float4(v[0], v[1], v[2], v[3]);

@@ -30,7 +30,7 @@ __global__ __launch_bounds__(256) void ln_mod_kernel(const float* __restrict__ x
     LnMod<MAXV> md;
     ln_mod_load<MAXV>(st, x, row, D);
     ln_mod_load_mod<MAXV>(md, shift, scale, D, (long long)(row / rows_per_batch) * mod_ld);
-    ln_mod_finish<MAXV, 0, 1>(st, out, row, D, eps, nullptr, nullptr, shift, scale, mod_ld, rows_per_batch, out_split, md);
+    ln_mod_finish<MAXV, 1>(st, out, row, D, eps, nullptr, nullptr, shift, scale, mod_ld, rows_per_batch, out_split, md);
     return;
   }
   ln_mod_row<MAXV>(x, out, row, D, eps, weight, bias, shift, scale, mod_ld, rows_per_batch, out_split);

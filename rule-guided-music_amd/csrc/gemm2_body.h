@@ -1,6 +1,5 @@
 // gemm2_body.h -- the tile body of the pre-split bf16x3 GEMM (gemm2.hip: design notes there), as a header: gemm2.hip instantiates it in
-// one-shape launches, chain.hip inside the persistent launch of a whole DiT forward (COH = 1: tile addressed directly, every output
-// stored device-coherent so that another workgroup of the SAME launch may consume it).
+// gemm2_kernel (one tile shape per launch) and in gemm2_dual_kernel (two tile shapes in one launch).
 #pragma once
 #include <math.h>
 #include <stdlib.h>
@@ -19,9 +18,9 @@ __device__ __forceinline__ void dma16(const void* gsrc, void* lds_dst) {
 
 // the kernel body: output tile `bid` (raster order) of batch element `z`.  A function so that ONE launch can mix tile shapes
 // (gemm2_dual_kernel below); gemm2_kernel is the plain one-shape wrapper.
-template <int BM, int BN, int WM, int WN, int ALOAD, int NSTAGE, int DBG = 0, int PIPE = 0, int COH = 0>
+template <int BM, int BN, int WM, int WN, int ALOAD, int NSTAGE, int DBG = 0, int PIPE = 0>
 __device__ __forceinline__ void gemm2_body(const GemmParams& p, const char* __restrict__ zero_page, int tiles_m, int tiles_n, int exp,
-                                           long long* __restrict__ dbg, const int bid, const int z, const int rec_bid, const int tid_in = -1) {
+                                           long long* __restrict__ dbg, const int bid, const int z, const int rec_bid) {
   constexpr int NW = WM * WN;
   constexpr int TM = BM / (WM * 32), TN = BN / (WN * 32);
   constexpr int STAGE = (BM + BN) * 128;        // bytes per ring stage: BM A rows then BN B rows, one 128-B line each
@@ -45,11 +44,11 @@ __device__ __forceinline__ void gemm2_body(const GemmParams& p, const char* __re
   const int first_m = grp * GROUP;
   const int gsz = min(tiles_m - first_m, GROUP);
   const int in_g = sid - grp * per_group;
-  // COH (chain.hip): the caller names the tile -- bid = row tile * tiles_n + column tile -- and consumes the output inside the same launch
-  const int m0 = COH ? (bid / tiles_n) * BM : (first_m + in_g % gsz) * BM;
-  const int n0 = COH ? (bid % tiles_n) * BN : (in_g / gsz) * BN;
+  // within a group of `gsz` row tiles the raster walks down the rows first, then to the next column tile
+  const int m0 = (first_m + in_g % gsz) * BM;
+  const int n0 = (in_g / gsz) * BN;
 
-  const int tid = tid_in >= 0 ? tid_in : (int)threadIdx.x;      // (chain.hip hands in an opaque copy: see there)
+  const int tid = threadIdx.x;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int lane = tid & 63, l31 = lane & 31, hh = lane >> 5;
 
@@ -297,7 +296,7 @@ __device__ __forceinline__ void gemm2_body(const GemmParams& p, const char* __re
     int pf_inc = 0, pf_left = 0;
     char* pf_dst = ring + NSTAGE * STAGE + wave * 256;
     bool pf_wave = false;
-    if (p.pf_kt > 0 && !COH) {
+    if (p.pf_kt > 0) {
       const int b_cnt = (BN + gsz - 1) / gsz;
       const int slot = wave * 64 + lane, rl = (in_g % gsz) * b_cnt + slot, row = n0 + rl;
       pf_wave = wave * 64 < b_cnt;
@@ -1010,10 +1009,7 @@ __device__ __forceinline__ void gemm2_body(const GemmParams& p, const char* __re
     // epilogue runs at the chip's write rate: non-temporal stores (the 57-76 MB of a qkv / fc1 output pass through the 32 MB of L2
     // anyway) take 1.7-4.4 % off those launches (tools/which_kernel.py, same box: 86.9 -> 85.4 us at 224 tiles, 98.3 -> 94.0 at 256).
     auto out16 = [&](float* dst, const float (&v)[4]) {
-      if constexpr (COH) {
-        const f32x4 nv = {v[0], v[1], v[2], v[3]};
-        store16_sc1(dst, nv);
-      } else if constexpr (PIPE == 5) {
+      if constexpr (PIPE == 5) {
         const f32x4 nv = {v[0], v[1], v[2], v[3]};
         if (p.st_plain) *reinterpret_cast<f32x4*>(dst) = nv;          // (A/B runs: RGM_ST_PLAIN, launch2)
         else __builtin_nontemporal_store(nv, reinterpret_cast<f32x4*>(dst));
@@ -1048,11 +1044,7 @@ __device__ __forceinline__ void gemm2_body(const GemmParams& p, const char* __re
           lo[q4] = (split_t)(v[q4] - (float)hi[q4]);
         }
         split_t* rowp = reinterpret_cast<split_t*>(Cb + (long long)row * p.ldc);
-        if constexpr (COH) {
-          store_split4_pair_sc1<1>(rowp, col, hi, lo);      // lanes (2k, 2k+1) own columns 8k' .. 8k'+7 of the same row
-        } else {
-          split_store(rowp, col, hi, lo);
-        }
+        split_store(rowp, col, hi, lo);
       } else if (exp != 4) {
         out16(Cb + (long long)row * p.ldc + col, v);
       }
@@ -1106,11 +1098,7 @@ __device__ __forceinline__ void gemm2_body(const GemmParams& p, const char* __re
                   }
                   split_t* rowp = p.C2 ? reinterpret_cast<split_t*>(p.C2 + (long long)z * p.sC + (long long)row * p.ldc2)
                                        : reinterpret_cast<split_t*>(Cb + (long long)row * p.ldc);
-                  if constexpr (COH) {
-                    store_split4_pair_sc1<1>(rowp, col, hi, lo);
-                  } else {
-                    split_store(rowp, col, hi, lo);
-                  }
+                  split_store(rowp, col, hi, lo);
                 } else {
                   if (exp != 4) out16(Cb + (long long)row * p.ldc + col, v);
                 }
@@ -1183,7 +1171,7 @@ __device__ __forceinline__ void gemm2_body(const GemmParams& p, const char* __re
         using I0 = std::integral_constant<int, 0>;
         using I1 = std::integral_constant<int, 1>;
         using I2 = std::integral_constant<int, 2>;
-        if (PIPE == 5 && !COH && p.out_split && p.split_pair == 2) {
+        if (PIPE == 5 && p.out_split && p.split_pair == 2) {
           if (p.act == 0) plain_rows8(I0{});
           else if (p.act == 1) plain_rows8(I1{});
           else plain_rows8(I2{});
@@ -1282,7 +1270,6 @@ __device__ __forceinline__ void gemm2_body(const GemmParams& p, const char* __re
     // one slab>) and never waits for a store.  With the residual loads behind the previous slab's stores (linear_rows) every slab
     // sat out its own round trip AND the previous slab's last store: 15-19 k cycles per slab (tools/conv_stamp.py).
     auto staged_dma_res = [&](int row0, float* rslab) {
-      if constexpr (COH) asm volatile("" ::: "memory");   // (COH stores are asm statements: keep the DMA where the counted waits expect it)
 #pragma unroll
       for (int j = 0; j < NJ; ++j) {
         const int row = row0 + j * RPI;
@@ -1290,7 +1277,6 @@ __device__ __forceinline__ void gemm2_body(const GemmParams& p, const char* __re
                                                                       : reinterpret_cast<const float*>(zero_page) + lc;
         dma16(src, reinterpret_cast<char*>(rslab) + j * 1024);
       }
-      if constexpr (COH) asm volatile("" ::: "memory");
     };
     auto staged_pass1 = [&](float* slab, const float* rslab, int row0, float4 g_lo, float4 g_hi, int bnd) {
       constexpr int U = 4;

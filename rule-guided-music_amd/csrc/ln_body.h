@@ -1,20 +1,20 @@
 // ln_body.h -- the row bodies of the DiT forward's two LayerNorm kernels as device functions: ln_mod_kernel (dit_kernels.hip) and
-// splitk_reduce_ln_kernel (gemm2.hip) wrap them one row per wave; chain.hip runs them as work items of the persistent forward.
+// splitk_reduce_ln_kernel (gemm2.hip) wrap them one row per wave.
 #pragma once
 #include "common.h"
 
 namespace rgm {
 
-// one wave = one row of ln_mod_kernel (dit_kernels.hip), in two steps so that a wave with several rows (chain.hip: four waves per CU and
-// nobody else to hide a row's round trip behind) can request all of them before it finishes the first: ln_mod_load, then ln_mod_finish.
-// COH = 1 (chain.hip; split output, D % 8 == 0): device-coherent 16-byte stores
+// one wave = one row of ln_mod_kernel (dit_kernels.hip), in two steps -- ln_mod_load, then ln_mod_finish -- so that the wave can request
+// the row AND the sample's modulation row (ln_mod_load_mod) before it finishes either: read behind the two wave reductions the modulation
+// row is a second dependent round trip, and with one wave per row nothing else hides it.
 template <int MAXV>
 struct LnRow {
   float4 v[MAXV];
 };
 template <int MAXV>
-__device__ __forceinline__ void ln_mod_load(LnRow<MAXV>& st, const float* __restrict__ x, const int row, int D, const int lane_in = -1) {
-  const int lane = lane_in >= 0 ? lane_in : (int)(threadIdx.x & 63);
+__device__ __forceinline__ void ln_mod_load(LnRow<MAXV>& st, const float* __restrict__ x, const int row, int D) {
+  const int lane = threadIdx.x & 63;
   const int nv = D >> 2;
   const float* xr = x + (long long)row * D;
 #pragma unroll
@@ -24,15 +24,16 @@ __device__ __forceinline__ void ln_mod_load(LnRow<MAXV>& st, const float* __rest
     st.v[i] = c < nv ? t : make_float4(0.f, 0.f, 0.f, 0.f);
   }
 }
-// the modulation row of a sample, loaded once for all the rows a wave holds (chain.hip): MOD = nullptr -> read per row as ln_mod_kernel does
+// the modulation row of a sample, requested together with the row (HAS_MOD = 1 in the finish step); HAS_MOD = 0: read from shift / scale
+// behind the reductions (rows with an affine weight, RGM_LN_PRELOAD=0)
 template <int MAXV>
 struct LnMod {
   float4 sc[MAXV], sh[MAXV];
 };
 template <int MAXV>
 __device__ __forceinline__ void ln_mod_load_mod(LnMod<MAXV>& md, const float* __restrict__ shift, const float* __restrict__ scale, int D,
-                                                long long mo, const int lane_in = -1) {
-  const int lane = lane_in >= 0 ? lane_in : (int)(threadIdx.x & 63);
+                                                long long mo) {
+  const int lane = threadIdx.x & 63;
   const int nv = D >> 2;
 #pragma unroll
   for (int i = 0; i < MAXV; ++i) {
@@ -42,13 +43,13 @@ __device__ __forceinline__ void ln_mod_load_mod(LnMod<MAXV>& md, const float* __
     md.sh[i] = ldg16(shift + mo + 4 * cc);
   }
 }
-template <int MAXV, int COH = 0, int HAS_MOD = 0>
+template <int MAXV, int HAS_MOD = 0>
 __device__ __forceinline__ void ln_mod_finish(const LnRow<MAXV>& st, float* __restrict__ out, const int row, int D,
                                               float eps, const float* __restrict__ weight,
                                               const float* __restrict__ bias, const float* __restrict__ shift,
                                               const float* __restrict__ scale, int mod_ld, int rows_per_batch,
-                                              int out_split, const LnMod<MAXV>& MOD = LnMod<MAXV>{}, const int lane_in = -1) {
-  const int lane = lane_in >= 0 ? lane_in : (int)(threadIdx.x & 63);
+                                              int out_split, const LnMod<MAXV>& MOD = LnMod<MAXV>{}) {
+  const int lane = threadIdx.x & 63;
   const int nv = D >> 2;
   float4 v[MAXV];
   float s = 0.f;
@@ -97,17 +98,13 @@ __device__ __forceinline__ void ln_mod_finish(const LnRow<MAXV>& st, float* __re
       lo[0] = (split_t)(y.x - (float)hi[0]); lo[1] = (split_t)(y.y - (float)hi[1]);
       lo[2] = (split_t)(y.z - (float)hi[2]); lo[3] = (split_t)(y.w - (float)hi[3]);
       split_t* rp = reinterpret_cast<split_t*>(out + (long long)row * D);
-      if constexpr (COH) {
-        store_split4_pair_sc1<1>(rp, c * 4, hi, lo);       // lanes (2k, 2k+1) hold chunks (2j, 2j+1): one 8-aligned group
-      } else {
-        store_split4_maybe_pair<1>(rp, c * 4, hi, lo);     // the same pairing, ordinary stores: 16 bytes per lane instead of 2 x 8
-      }
+      store_split4_maybe_pair<1>(rp, c * 4, hi, lo);       // lanes (2k, 2k+1) hold chunks (2j, 2j+1), one 8-aligned group: 16 bytes per lane, not 2 x 8
     } else {
       orow[c] = y;
     }
   }
 }
-template <int MAXV, int COH = 0>
+template <int MAXV>
 __device__ __forceinline__ void ln_mod_row(const float* __restrict__ x, float* __restrict__ out, const int row, int D,
                                            float eps, const float* __restrict__ weight,
                                            const float* __restrict__ bias, const float* __restrict__ shift,
@@ -115,12 +112,11 @@ __device__ __forceinline__ void ln_mod_row(const float* __restrict__ x, float* _
                                            int out_split) {
   LnRow<MAXV> st;
   ln_mod_load<MAXV>(st, x, row, D);
-  ln_mod_finish<MAXV, COH>(st, out, row, D, eps, weight, bias, shift, scale, mod_ld, rows_per_batch, out_split);
+  ln_mod_finish<MAXV>(st, out, row, D, eps, weight, bias, shift, scale, mod_ld, rows_per_batch, out_split);
 }
 
 
 // one wave = one row of splitk_reduce_ln_kernel (gemm2.hip).  LN = 0: the reduce alone (the last block of a forward has no next LayerNorm).
-// COH = 1 (chain.hip): the reduced row and the LayerNorm row are stored device-coherent, 16 bytes per lane.
 // (two steps like ln_mod_row: splitk_reduce_load -- the S partial sums and the residual of a row; the bias and the gate row, shared by the
 // rows of a sample, come with splitk_reduce_shared -- then splitk_reduce_ln_finish)
 template <int MAXV, int S>
@@ -132,8 +128,8 @@ struct RedShared {
   float4 bq[MAXV], gq[MAXV];
 };
 template <int MAXV>
-__device__ __forceinline__ void splitk_reduce_shared(RedShared<MAXV>& sh, const GemmParams& p, const int row, const int lane_in = -1) {
-  const int lane = lane_in >= 0 ? lane_in : (int)(threadIdx.x & 63);
+__device__ __forceinline__ void splitk_reduce_shared(RedShared<MAXV>& sh, const GemmParams& p, const int row) {
+  const int lane = threadIdx.x & 63;
   const int nv = p.N >> 2;
 #pragma unroll
   for (int i = 0; i < MAXV; ++i) {
@@ -146,8 +142,8 @@ __device__ __forceinline__ void splitk_reduce_shared(RedShared<MAXV>& sh, const 
   }
 }
 template <int MAXV, int S>
-__device__ __forceinline__ void splitk_reduce_load(RedRow<MAXV, S>& st, const float* __restrict__ P, const GemmParams& p, const int row, const int lane_in = -1) {
-  const int lane = lane_in >= 0 ? lane_in : (int)(threadIdx.x & 63);
+__device__ __forceinline__ void splitk_reduce_load(RedRow<MAXV, S>& st, const float* __restrict__ P, const GemmParams& p, const int row) {
+  const int lane = threadIdx.x & 63;
   const int nv = p.N >> 2;
   const long long MN = (long long)p.M * p.N;
   // one wave holds the row and there are only M waves (1024 at B = 4): every load of the row -- S partial sums, bias, gate, residual
@@ -169,10 +165,10 @@ __device__ __forceinline__ void splitk_reduce_load(RedRow<MAXV, S>& st, const fl
     }
   }
 }
-template <int MAXV, int S, int COH = 0, int LN = 1, int HAS_MOD = 0>
+template <int MAXV, int S, int LN = 1, int HAS_MOD = 0>
 __device__ __forceinline__ void splitk_reduce_ln_finish(const RedRow<MAXV, S>& st, const RedShared<MAXV>& sh, const GemmParams& p, const int row,
-                                                        const LnMod<MAXV>& MOD = LnMod<MAXV>{}, const int lane_in = -1) {
-  const int lane = lane_in >= 0 ? lane_in : (int)(threadIdx.x & 63);
+                                                        const LnMod<MAXV>& MOD = LnMod<MAXV>{}) {
+  const int lane = threadIdx.x & 63;
   const int nv = p.N >> 2;
   float4 v[MAXV];
   float s = 0.f;
@@ -193,12 +189,7 @@ __device__ __forceinline__ void splitk_reduce_ln_finish(const RedRow<MAXV, S>& s
       if (p.gate) { w[0] *= sh.gq[i].x; w[1] *= sh.gq[i].y; w[2] *= sh.gq[i].z; w[3] *= sh.gq[i].w; }
       if (p.res) { w[0] += st.rq[i].x; w[1] += st.rq[i].y; w[2] += st.rq[i].z; w[3] += st.rq[i].w; }
       v[i] = make_float4(w[0], w[1], w[2], w[3]);
-      if constexpr (COH) {
-        const f32x4 wv = {w[0], w[1], w[2], w[3]};
-        store16_sc1(p.C + (long long)row * p.ldc + col, wv);
-      } else {
-        *reinterpret_cast<float4*>(p.C + (long long)row * p.ldc + col) = v[i];
-      }
+      *reinterpret_cast<float4*>(p.C + (long long)row * p.ldc + col) = v[i];
     }
     s += (v[i].x + v[i].y) + (v[i].z + v[i].w);
   }
@@ -238,23 +229,19 @@ __device__ __forceinline__ void splitk_reduce_ln_finish(const RedRow<MAXV, S>& s
       lo[0] = (split_t)(y.x - (float)hi[0]); lo[1] = (split_t)(y.y - (float)hi[1]);
       lo[2] = (split_t)(y.z - (float)hi[2]); lo[3] = (split_t)(y.w - (float)hi[3]);
       split_t* rp = reinterpret_cast<split_t*>(p.ln_out + (long long)row * p.N);
-      if constexpr (COH) {
-        store_split4_pair_sc1<1>(rp, c * 4, hi, lo);
-      } else {
-        store_split4_maybe_pair<1>(rp, c * 4, hi, lo);
-      }
+      store_split4_maybe_pair<1>(rp, c * 4, hi, lo);
     } else {
       orow[c] = y;
     }
   }
 }
-template <int MAXV, int S, int COH = 0, int LN = 1>
+template <int MAXV, int S, int LN = 1>
 __device__ __forceinline__ void splitk_reduce_ln_row(const float* __restrict__ P, const GemmParams& p, const int row) {
   RedRow<MAXV, S> st;
   RedShared<MAXV> sh;
   splitk_reduce_shared<MAXV>(sh, p, row);
   splitk_reduce_load<MAXV, S>(st, P, p, row);
-  splitk_reduce_ln_finish<MAXV, S, COH, LN>(st, sh, p, row);
+  splitk_reduce_ln_finish<MAXV, S, LN>(st, sh, p, row);
 }
 
 

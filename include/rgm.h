@@ -504,6 +504,29 @@ int rgm_collage_split(const float* img, float* wins, float* halves, int B, int C
 int rgm_collage_merge(const float* full, const float* half, float* out, int B, int C, int h, int n, int overlap,
                       int circle, int is_avg, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Particle rule guidance (sequential Monte Carlo)          csrc/particles.hip, docs/rounds/particles.md
+ * ---------------------------------------------------------------------------------------------- */
+/* One weighting-and-resampling step for B groups of n particles, particle k of group b at index k*B + b (SCG's candidate layout).
+ * Per group, in float64:
+ *   r_k   = reward[k], with NaN and +inf counted as -inf (a broken particle dies; rgm_scg_select keeps argmax's NaN-as-max instead)
+ *   l_k   = logw[k] + lambda (r_k - r_prev[k]); -inf where r_k or logw[k] is -inf.  r_prev[k] <- r_k where r_k is finite.
+ *   w_k   = exp(l_k - max l) / sum, ESS = 1 / sum w_k^2 -> ess_out[b]
+ *   resample iff ESS < ess_frac n (ess_frac <= 0: never, > 1: always).  Every weight 0: no resampling, logw <- 0, resampled[b] = -1,
+ *   ess_out[b] = 0, anc[k] = k.
+ *   resampling is systematic: c_j = w_0 + ... + w_j in ascending j, c_{n-1} counted as +inf, anc[k] = min{j : c_j > (k + u) / n}
+ *   (strict: a zero-weight particle is never chosen); then logw <- 0, r_prev[k] <- r_prev[anc[k]], resampled[b] = 1.
+ *   otherwise anc[k] = k, logw[k] <- l_k - logsumexp(l) + log n (uniform weights are 0), resampled[b] = 0.
+ * u: B float64 on the device in [0, 1), or NULL: u_b = (w0 + 0.5) 2^-32 with w0 the first word of Philox4x32-10 block
+ * (seed, counter + b) -- the generator of rgm_randn.  logw (float64) and r_prev (float32) are updated in place; anc int32 (n, B),
+ * ess_out float64 (B), resampled int32 (B).  1 <= n <= 1024.  One workgroup per group, every sum with one owner in ascending k: a
+ * group's result depends neither on B nor on its position, and launches repeat bit for bit. */
+int rgm_particle_resample(const float* reward, double* logw, float* r_prev, double lambda, double ess_frac, const double* u,
+                          uint64_t seed, uint64_t counter, int32_t* anc, double* ess_out, int32_t* resampled, int n, int B, void* stream);
+/* dst[(k, b), :] = src[(anc[k, b], b), :] for n x B rows of E floats, out of place (the ranges must not overlap); an ancestor outside
+ * [0, n) is clamped into it.  16-byte copies where E % 4 == 0 and both bases are 16-byte aligned, 4-byte ones otherwise. */
+int rgm_gather_rows(const float* src, float* dst, const int32_t* anc, int n, int B, int E, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -33,6 +33,8 @@ ddim_reverse_sample / ddim_reverse_sample_loop (DDIM inversion, rgm_ddim_reverse
 Beyond the reference: dpmpp_sample / dpmpp_sample_loop(_progressive), DPM-Solver++(2M) -- a second-order multistep solver in data-prediction
 form, as the probability-flow ODE (eta = 0) or its SDE form (eta = 1) -- one rgm_dpmpp_step launch per step on coefficient tables built
 here in float64 (dpmpp_tables); meant for a logSNR-uniform chain (respace.space_timesteps "logsnrN").
+particle_sample_loop(_progressive): particle rule guidance, a sequential Monte Carlo sampler beside SCG -- n chains per excerpt from one
+n B-row forward per step, weighted by the change in rule score and resampled on the device (rgm_particle_resample, rgm_gather_rows).
 """
 import ctypes as C
 import enum
@@ -1227,6 +1229,196 @@ class GaussianDiffusion:
                 scg_kwargs=scg_kwargs, edit_kwargs=edit_kwargs, record=record):
             pass
         return final["sample"]
+
+    # ------------------------------------------------------------------ particle rule guidance (sequential Monte Carlo beside SCG)
+    PARTICLE_KEYS = ("lambda", "ess", "every", "t_start", "t_stop")
+    MAX_PARTICLES = 1024
+
+    def _particle_check(self, num_particles, sampler, particle_kwargs, eta=1.0, dpmpp_order=2, guidance_kwargs=None, edit_kwargs=None,
+                        scg_kwargs=None):
+        """What the particle loop cannot do, refused by name before anything is computed (no device is touched)."""
+        n = int(num_particles)
+        if n < 1 or n > self.MAX_PARTICLES:
+            raise ValueError(f"particle_sample_loop: num_particles = {num_particles!r}; rgm_particle_resample takes 1 .. {self.MAX_PARTICLES}")
+        if sampler not in ("ddpm", "ddim", "dpmpp"):
+            raise ValueError(f"particle_sample_loop: sampler = {sampler!r}; one of 'ddpm', 'ddim', 'dpmpp'")
+        if eta != 1:
+            raise ValueError(f"particle_sample_loop: eta = {eta!r}; duplicated particles diverge through the noise of a stochastic step -- "
+                             "eta = 1 only (the ODE, eta = 0, has none)")
+        if sampler == "dpmpp" and dpmpp_order not in (1, 2):
+            raise ValueError(f"particle_sample_loop: dpmpp_order = {dpmpp_order!r}; DPM-Solver++(2M) is second order (or 1)")
+        if edit_kwargs is not None:
+            raise NotImplementedError("particle_sample_loop: edit_kwargs (replacement-based editing) is not supported")
+        if scg_kwargs is not None:
+            raise ValueError("particle_sample_loop: scg_kwargs together with particles -- the particle loop replaces the SCG search; "
+                             "give the rule weights in particle_kwargs")
+        if guidance_kwargs is not None and getattr(guidance_kwargs, "method", None) == "dps":
+            raise NotImplementedError("particle_sample_loop: DPS guidance_kwargs are not supported (a gradient cond_fn passes through)")
+        if guidance_kwargs is not None and getattr(getattr(guidance_kwargs, "dc", None), "base", 0) > 0:
+            raise NotImplementedError("particle_sample_loop: segment mode (dc.base > 0) is not supported; a DiffCollage model function "
+                                      "is just a model and works")
+        if self.model_mean_type == ModelMeanType.PREVIOUS_X:
+            raise NotImplementedError("particle_sample_loop: a PREVIOUS_X network is not supported (the particles are scored on an x0 "
+                                      "estimate formed from eps)")
+        if self._learned():
+            raise NotImplementedError("particle_sample_loop: learned-variance networks (learn_sigma=True) are not supported")
+        pk = dict(particle_kwargs or {})
+        T = self.num_timesteps
+        cfg = dict(lam=float(pk.get("lambda", 1.0)), ess=float(pk.get("ess", 0.5)), every=int(pk.get("every", 1)),
+                   t_start=int(pk.get("t_start", T)), t_stop=int(pk.get("t_stop", 0)))
+        if not math.isfinite(cfg["lam"]) or math.isnan(cfg["ess"]):
+            raise ValueError(f"particle_sample_loop: lambda = {cfg['lam']!r}, ess = {cfg['ess']!r} must be numbers (lambda finite)")
+        if cfg["every"] < 1:
+            raise ValueError(f"particle_sample_loop: every = {cfg['every']!r} must be at least 1")
+        cfg["weights"] = {k: float(v) for k, v in pk.items() if k not in self.PARTICLE_KEYS}
+        return n, cfg
+
+    def _particle_reward(self, lat, t, model_kwargs, embed_model, scale_factor, weights, reward_fn):
+        """(N,) float32 reward of latent rows: reward_fn(lat, t), or the weighted sum of -LOSS(rule(decode(lat)), target) over the
+        target rules -- the total of scg_sample's table."""
+        if reward_fn is not None:
+            return reward_fn(lat, t).float().reshape(-1).contiguous()
+        roll = _decode(lat, embed_model, scale_factor=scale_factor) if embed_model is not None else lat
+        total = None
+        for name, target in model_kwargs["rule"].items():
+            lp = -LOSS_DICT[name](_extract_rule(name, roll), target)
+            total = lp * weights.get(name, 1.) if total is None else total + lp * weights.get(name, 1.)
+        return total.float().reshape(-1).contiguous()
+
+    def _particle_resample(self, state, reward, lam, ess, u):
+        """One rgm_particle_resample launch on the loop's state; u: (B,) float64 on the device, or None for the Philox draw (B counters
+        reserved from the noise stream like any other draw).  Returns the (n, B) int32 ancestors."""
+        n, B = state["n"], state["B"]
+        dev = reward.device
+        anc = th.empty((n, B), dtype=th.int32, device=dev)
+        seed = counter = 0
+        if u is None:
+            if self.noise is None:
+                self.noise = PhiloxNoise()
+            # whole Philox blocks no normal of the stream shares: blocks [counter, counter + B) lie inside the reserved positions
+            counter = (self.noise.reserve(4 * (B + 1)) + 3) >> 2
+            seed = self.noise.seed
+        else:
+            _rgm.require_cuda(u)
+            assert u.dtype == th.float64 and u.numel() == B, f"u: {B} float64 values, one per group, got {u.dtype} {tuple(u.shape)}"
+            u = u.contiguous()
+        with th.cuda.device(dev):
+            _rgm.check(_rgm.lib.rgm_particle_resample(_rgm.ptr(reward), _rgm.ptr(state["logw"]), _rgm.ptr(state["r_prev"]), float(lam),
+                                                      float(ess), _rgm.ptr(u), C.c_uint64(seed), C.c_uint64(counter), _rgm.ptr(anc),
+                                                      _rgm.ptr(state["ess"]), _rgm.ptr(state["resampled"]), n, B, _rgm.current_stream()))
+        return anc
+
+    @staticmethod
+    def _gather_rows(src, anc):
+        """row (k, b) <- row (anc[k, b], b), out of place (rgm_gather_rows)"""
+        src = src.float().contiguous()
+        n, B = anc.shape
+        dst = th.empty_like(src)
+        with th.cuda.device(src.device):
+            _rgm.check(_rgm.lib.rgm_gather_rows(_rgm.ptr(src), _rgm.ptr(dst), _rgm.ptr(anc), n, B, src.numel() // (n * B),
+                                                _rgm.current_stream()))
+        return dst
+
+    def particle_sample_loop_progressive(self, model, shape, num_particles, sampler="ddpm", particle_kwargs=None, model_kwargs=None,
+                                         embed_model=None, scale_factor=1., clip_denoised=True, denoised_fn=None, cond_fn=None, t_end=0,
+                                         noise=None, device=None, progress=False, reward_fn=None, dpmpp_order=2, u_fn=None,
+                                         guidance_kwargs=None, edit_kwargs=None, scg_kwargs=None, eta=1.0):
+        """The particle chain, one dict {'sample', 'pred_xstart'} of n B rows per step; the result dict of particle_sample_loop is left
+        in self.last_particles behind the last step.  See particle_sample_loop."""
+        n, cfg = self._particle_check(num_particles, sampler, particle_kwargs, eta, dpmpp_order, guidance_kwargs, edit_kwargs, scg_kwargs)
+        model_kwargs = model_kwargs or {}
+        if reward_fn is None and not model_kwargs.get("rule"):
+            raise ValueError("particle_sample_loop: nothing to score -- give model_kwargs['rule'] targets or a reward_fn")
+        if device is None:
+            device = next(model.parameters()).device
+        assert isinstance(shape, (tuple, list))
+        B = int(shape[0])
+        rows = (n * B,) + tuple(shape[1:])
+        # conditioning of the n B rows: particle k of group b is row k B + b, so per-group tensors repeat n times
+        mk = dict(model_kwargs)
+        if th.is_tensor(mk.get("y")):
+            mk["y"] = mk["y"].repeat(n)
+        if mk.get("rule"):
+            mk["rule"] = {k: v.repeat(n, *([1] * (v.dim() - 1))) for k, v in mk["rule"].items()}
+        self.t_end = t_end
+        x = noise if noise is not None else self._draw(rows, device)
+        assert tuple(x.shape) == rows, f"noise {tuple(x.shape)}: the particle loop starts from n B = {rows[0]} rows"
+        state = dict(n=n, B=B, logw=th.zeros(n * B, dtype=th.float64, device=device), r_prev=th.zeros(n * B, dtype=th.float32, device=device),
+                     ess=th.zeros(B, dtype=th.float64, device=device), resampled=th.zeros(B, dtype=th.int32, device=device))
+        count = th.zeros(B, dtype=th.int64, device=device)
+        wrapped, wcond = self._wrap_model(model), (self._wrap_model(cond_fn) if cond_fn is not None else None)
+        indices = list(range(self.num_timesteps))[::-1]
+        if t_end:
+            indices = indices[:-t_end]
+        if progress:
+            from tqdm.auto import tqdm
+            indices = tqdm(indices)
+        x0_prev, t = None, None
+        for i in indices:
+            t = th.full((n * B,), i, dtype=th.int64, device=device)
+            self._t_host = i
+            try:
+                with th.no_grad():
+                    eps = self._model_eps(x, self._eps_net(wrapped, x, t, **mk), t, denoised_fn)
+                    if cfg["t_stop"] <= i < cfg["t_start"] and (cfg["t_start"] - 1 - i) % cfg["every"] == 0:
+                        x0 = self._predict_xstart_from_eps(x, t, eps)
+                        reward = self._particle_reward(x0, t, mk, embed_model, scale_factor, cfg["weights"], reward_fn)
+                        anc = self._particle_resample(state, reward, cfg["lam"], cfg["ess"], u_fn(i, B) if u_fn is not None else None)
+                        count += (state["resampled"] == 1)
+                        # eps depends on (x, t, y) alone and y is shared within a group: the ancestor's eps is the duplicate's eps
+                        x, eps = self._gather_rows(x, anc), self._gather_rows(eps, anc)
+                        if x0_prev is not None:
+                            x0_prev = self._gather_rows(x0_prev, anc)
+                    grad = None
+                    if wcond is not None and (guidance_kwargs is None or self._use_guidance(guidance_kwargs, t)):
+                        grad = wcond(x, self._scale_timesteps(t), **mk)
+                    z = self._draw(rows, device)
+                    if sampler == "dpmpp":
+                        x, x0, _ = self._dpm_step(x, eps, grad, x0_prev, z, t, clip_denoised, order=dpmpp_order, eta=1.0)
+                        x0_prev = x0
+                    else:
+                        x, x0, _ = self._step(sampler, x, eps, grad, z, t, clip_denoised, eta=1.0)
+            finally:
+                self._t_host = None
+            yield {"sample": x, "pred_xstart": x0}
+        with th.no_grad():
+            # the final weighting: the reward of the sample itself, one weight update, no resampling
+            reward = self._particle_reward(x, t, mk, embed_model, scale_factor, cfg["weights"], reward_fn)
+            self._particle_resample(state, reward, cfg["lam"], 0.0, th.zeros(B, dtype=th.float64, device=device))
+            best = th.empty((B,) + tuple(shape[1:]), dtype=th.float32, device=device)
+            max_ind = th.empty(B, dtype=th.int64, device=device)
+            xs = x.float().contiguous()
+            with th.cuda.device(device):
+                _rgm.check(_rgm.lib.rgm_scg_select(_rgm.ptr(xs), _rgm.ptr(reward), _rgm.ptr(best), _rgm.ptr(max_ind), n, B,
+                                                   xs.numel() // (n * B), _rgm.current_stream()))
+        self.last_particles = {"sample": x, "log_weights": state["logw"].view(n, B), "reward": reward.view(n, B), "best": best,
+                               "max_ind": max_ind, "resampled_steps": count}
+
+    def particle_sample_loop(self, model, shape, num_particles, sampler="ddpm", particle_kwargs=None, model_kwargs=None, embed_model=None,
+                             scale_factor=1., clip_denoised=True, denoised_fn=None, cond_fn=None, t_end=0, noise=None, device=None,
+                             progress=False, reward_fn=None, dpmpp_order=2, u_fn=None, guidance_kwargs=None, edit_kwargs=None,
+                             scg_kwargs=None, eta=1.0):
+        """Particle rule guidance: B groups (`shape` is the group shape (B, C, H, W)) of num_particles chains, particle k of group b at
+        row k B + b, each propagated by the stochastic step of `sampler` ('ddpm', 'ddim' at eta = 1, 'dpmpp' in its SDE form) from ONE
+        n B-row forward per step.  On a scored step -- chain index i in [t_stop, t_start) with (t_start - 1 - i) % every == 0 -- the
+        particles are weighted by exp(lambda (r - r_prev)), r the rule score of their x0 estimate (the weighted total of scg_sample's
+        table, or reward_fn(x0_rows, t) -> (n B,)), and resampled systematically where the effective sample size falls below ess n
+        (rgm_particle_resample: the decision stays on the device; the ancestor gather always runs).  The weights' product telescopes to
+        exp(lambda r(x_0)): the weighted particles target p(x0) exp(lambda r(x0)).  particle_kwargs: lambda (1.0), ess (0.5), every (1),
+        t_start (chain length), t_stop (0) and per-rule weights by name as in scg_kwargs.  u_fn(i, B) -> (B,) float64 on the device
+        replaces the Philox draw of the resampling offsets (tests; nothing is then reserved from the noise stream).  A gradient cond_fn
+        is applied after the gather, on every step (or as guidance_kwargs' schedule says).  edit_kwargs, scg_kwargs, DPS or segment-mode
+        guidance_kwargs, eta != 1, PREVIOUS_X and learned-variance networks raise.  Under torch.distributed every rank computes
+        everything.  Returns (and keeps as self.last_particles) {'sample' (n B rows), 'log_weights' (n, B) float64, normalised so that
+        uniform weights are 0, 'reward' (n, B) of the final samples, 'best' (B rows: the first arg-max of the final reward), 'max_ind',
+        'resampled_steps' (B,) resampling count per group}.  docs/rounds/particles.md."""
+        for _ in self.particle_sample_loop_progressive(
+                model, shape, num_particles, sampler=sampler, particle_kwargs=particle_kwargs, model_kwargs=model_kwargs,
+                embed_model=embed_model, scale_factor=scale_factor, clip_denoised=clip_denoised, denoised_fn=denoised_fn, cond_fn=cond_fn,
+                t_end=t_end, noise=noise, device=device, progress=progress, reward_fn=reward_fn, dpmpp_order=dpmpp_order, u_fn=u_fn,
+                guidance_kwargs=guidance_kwargs, edit_kwargs=edit_kwargs, scg_kwargs=scg_kwargs, eta=eta):
+            pass
+        return self.last_particles
 
     # ------------------------------------------------------------------ inversion and evaluation (a FROZEN network: forwards only)
     def _predict_xstart_from_xprev(self, x_t, t, xprev):

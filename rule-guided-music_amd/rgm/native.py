@@ -83,6 +83,8 @@ def _load():
         "rgm_kde_pdf": (C.c_int, [vp, i32, vp, i32, vp, vp, sz, vp]),
         "rgm_set_kl_oa_workspace": (sz, [i32, i32, i32, i32]),
         "rgm_set_kl_oa": (C.c_int, [vp, i32, vp, i32, i32, i32, vp, vp, sz, vp]),
+        "rgm_particle_resample": (C.c_int, [vp, vp, vp, C.c_double, C.c_double, vp, C.c_uint64, C.c_uint64, vp, vp, vp, i32, i32, vp]),
+        "rgm_gather_rows": (C.c_int, [vp, vp, vp, i32, i32, i32, vp]),
         "rgm_bucketize": (C.c_int, [vp, vp, i32, vp, i32, vp]),
         "rgm_row_loss": (C.c_int, [vp, vp, vp, i32, i32, i32, vp]),
         "rgm_collage_split": (C.c_int, [vp, vp, vp, i32, i32, i32, i32, i32, i32, vp]),

@@ -110,6 +110,7 @@ def write_run_metadata(save_dir, args, extra=None):
     meta["chord_profile"] = getattr(args, "chord_profile", "krumhansl") if meta["chord_backend"] == "native" else None
     meta["note_stats"] = bool(getattr(args, "note_stats", False))   # notes.* columns in results.csv (docs/rounds/notes.md)
     meta["long_backward"] = bool(long_backward())     # RGM_LONG_BACKWARD / set_long_backward: guidance beyond 256 / 288 tokens was allowed
+    meta["particles"] = particle_metadata(args)       # --particles: the particle loop in place of the SCG search (docs/rounds/particles.md)
     meta.update(extra or {})
     with open(os.path.join(save_dir, "run_metadata.json"), "w") as f:
         json.dump(meta, f, indent=1)
@@ -161,6 +162,37 @@ def sampler_metadata(args):
         return {"name": "config", "timestep_respacing": getattr(args, "timestep_respacing", "")}
     return {"name": "dpmpp", "timestep_respacing": args.timestep_respacing, "steps": int(args.dpmpp_steps),
             "order": int(args.dpmpp_order), "eta": float(args.dpmpp_eta)}
+
+
+def particle_metadata(args):
+    n = int(getattr(args, "particles", 0) or 0)
+    if n < 2:
+        return None
+    return {"num_particles": n, "lambda": float(args.particle_lambda), "ess": float(args.particle_ess), "every": int(args.particle_every),
+            "keep": args.particle_keep}
+
+
+def particle_loop(args, config, diffusion):
+    """--particles n >= 2: the config's target rules under diffusion.particle_sample_loop on the chain choose_sampler picked, forced
+    stochastic (DDPM, DDIM at eta = 1, the SDE form of DPM-Solver++).  The rule weights are the YAML's `scg` block where present
+    (scg.num_samples is ignored); every step is scored unless --particle_every says otherwise.  A gradient cond_fn passes through under
+    the YAML's guidance schedule; DPS and segment-mode configs raise (GaussianDiffusion._particle_check).  Returns
+    sample_fn(model, shape, **the sampling loops' keywords) -> the particle loop's result dict."""
+    n = int(args.particles)
+    if n < 2:
+        raise ValueError(f"--particles {n}: 0 (off) or at least 2 particles per excerpt")
+    pk = {k: v for k, v in vars(getattr(config, "scg", None) or argparse.Namespace()).items() if k != "num_samples"}
+    pk.update({"lambda": float(args.particle_lambda), "ess": float(args.particle_ess), "every": int(args.particle_every)})
+    name = "dpmpp" if args.sampler == "dpmpp" else ("ddim" if config.sampling.use_ddim else "ddpm")
+
+    def sample_fn(model, shape, clip_denoised, model_kwargs, device, cond_fn, embed_model, scale_factor, guidance_kwargs, scg_kwargs,
+                  t_end, record, progress):
+        del scg_kwargs, record                       # the particle loop replaces the SCG search and keeps no per-step records
+        return diffusion.particle_sample_loop(model, shape, n, sampler=name, particle_kwargs=pk, model_kwargs=model_kwargs,
+                                              embed_model=embed_model, scale_factor=scale_factor, clip_denoised=clip_denoised,
+                                              cond_fn=cond_fn, t_end=t_end, device=device, progress=progress,
+                                              dpmpp_order=int(args.dpmpp_order), guidance_kwargs=guidance_kwargs)
+    return sample_fn
 
 
 def targets_from_npz(path, target_rules, batch_size, device):
@@ -325,7 +357,7 @@ def build_pipeline(args, config, device):
 
 
 def main(argv=None):
-    args = add_note_stats_arguments(add_sampler_arguments(create_argparser())).parse_args(argv)
+    args = add_particle_arguments(add_note_stats_arguments(add_sampler_arguments(create_argparser()))).parse_args(argv)
     args.dir = output_dir_for(args.config_path, args.class_label)
     from rgm import native as _native
     _native.set_gemm_precision(args.gemm_precision)      # "bf16x3_presplit" / "bf16x3" (fast, fp32-grade) or "fp32" (exact fp32 MFMA)
@@ -361,7 +393,8 @@ def main(argv=None):
     os.makedirs(os.path.expanduser(save_dir), exist_ok=True)
     if args.save_files and rank0:
         write_run_metadata(save_dir, args)
-    sample_fn = sampler_loop(args, config, diffusion)
+    particles = int(args.particles) != 0
+    sample_fn = particle_loop(args, config, diffusion) if particles else sampler_loop(args, config, diffusion)
     use_scg = bool(getattr(config.guidance, "scg", getattr(config.guidance, "beam", False)))
 
     logger.log("sampling...")
@@ -373,6 +406,16 @@ def main(argv=None):
             cond_fn=cond_fn_used, embed_model=embed_model if config.guidance.vae else None, scale_factor=args.scale_factor,
             guidance_kwargs=config.guidance, scg_kwargs=vars(config.scg) if use_scg else None,
             t_end=config.sampling.t_end, record=args.record, progress=args.progress)
+        rules_of, classes_of, particle_cols = model_kwargs["rule"], classes, {}
+        if particles:                                      # 'best': B rolls, results.csv as ever; 'all': n B rolls, row k B + b = particle k of excerpt b
+            res = sample
+            sample = res["best"] if args.particle_keep == "best" else res["sample"]
+            if args.particle_keep == "all":
+                n = int(args.particles)
+                rules_of = {k: v.repeat(n, 1) for k, v in model_kwargs["rule"].items()}
+                classes_of = classes.repeat(n) if classes is not None else None
+                particle_cols = {"particle": th.arange(n).repeat_interleave(args.batch_size).tolist(),
+                                 "log_weight": res["log_weights"].reshape(-1).cpu().tolist()}
         if KEEP_FLOAT_ROLLS is not None:        # parity tests: the float roll explains every uint8 difference (boundary adjacency)
             from guided_diffusion.gaussian_diffusion import _decode
             with _native.gemm_precision_scope("fp32" if midi_util.FINAL_DECODE_EXACT else None):   # the final decode's own arithmetic
@@ -381,11 +424,11 @@ def main(argv=None):
         note_cols = note_stats_columns(sample) if args.note_stats else {}                  # on the device, before the roll leaves it
         arr = sample.cpu().numpy().transpose(0, 3, 1, 2)                                   # (B, 3, 128, T) uint8
         if args.save_files and rank0:
-            midi_util.save_piano_roll_midi(arr, save_dir, args.fs, y=classes.cpu().numpy() if classes is not None else None,
-                                           save_ind=count_samples)
+            midi_util.save_piano_roll_midi(arr, save_dir, args.fs, y=classes_of.cpu().numpy() if classes_of is not None else None,
+                                           save_ind=count_samples * (arr.shape[0] // args.batch_size))
         generated = th.from_numpy(arr.astype(np.float32)) / 63.5 - 1
-        results = midi_util.eval_rule_loss(generated, model_kwargs["rule"])
-        for name, col in note_cols.items():
+        results = midi_util.eval_rule_loss(generated, rules_of)
+        for name, col in list(note_cols.items()) + list(particle_cols.items()):
             results[name] = col
         all_results = pd.concat([all_results, results], ignore_index=True)
         if args.save_files and rank0:
@@ -449,6 +492,23 @@ def add_note_stats_arguments(parser):
                    help="True: mgeval's note statistics of every saved roll (used pitches, pitch range, average IOI, pitch-class histogram, "
                         "mean velocity / duration, notes per second, transition matrix) as notes.* columns of results.csv, their means in "
                         "summary.csv; computed on the device (docs/rounds/notes.md)")
+    return parser
+
+
+def add_particle_arguments(parser):
+    """--particles and its options: particle rule guidance (sequential Monte Carlo) in place of the SCG search, kept out of
+    create_argparser's defaults like the two groups above (docs/rounds/particles.md)."""
+    g = parser.add_argument_group("particle rule guidance")
+    g.add_argument("--particles", type=int, default=0,
+                   help="n >= 2: run the config's target rules under the particle loop with n particles per excerpt (rule weights from the "
+                        "YAML's scg block, scg.num_samples ignored; the sampler forced stochastic); 0: off")
+    g.add_argument("--particle_lambda", type=float, default=1.0, help="the tilt: the particles target p(x0) exp(lambda r(x0))")
+    g.add_argument("--particle_ess", type=float, default=0.5,
+                   help="resample a group where its effective sample size falls below this fraction of n (<= 0 never, > 1 always)")
+    g.add_argument("--particle_every", type=int, default=1, help="score and resample on every k-th step")
+    g.add_argument("--particle_keep", default="best", choices=["best", "all"],
+                   help="'best': one roll per excerpt, the particle of the highest final reward; 'all': every particle's roll, with "
+                        "`particle` and `log_weight` columns in results.csv")
     return parser
 
 

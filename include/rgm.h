@@ -393,6 +393,29 @@ int rgm_note_stats(const uint8_t* roll, long long stride_n, long long stride_c, 
  * 1..4, 9, 10, 18..21; a threshold at -0.95 would lose 1..3 (3 / 63.5 - 1 = -0.9528).  A caller who wants the decode's threshold
  * on a continuous roll applies it first (docs/rounds/notes.md). */
 int rgm_roll_to_u8(const float* roll, uint8_t* out, int N, int C, int T, void* stream);
+/* Standard MIDI Files on the device                      guided_diffusion/midi_util.py:67-93 (save_piano_roll_midi) over
+ * music_rule_guidance/piano_roll_to_chord.py:167-275 (piano_roll_to_pretty_midi) and the fork's pretty_midi/pretty_midi.py:1341-1520 (write);
+ * csrc/midi.hip, docs/rounds/midi.md.  The roll is what rgm_note_stats takes (uint8, four byte strides, C = 1 / 2 / 3, 1 <= T <= 32768,
+ * first_column_onsets) and is never written.  The file is byte for byte the one the host writer (SimpleMIDI.write) makes of the same roll:
+ * format 1, 220 ticks per quarter, a tempo track and one instrument on channel 0, a status byte on every message, deltas of 1 to 3 bytes.
+ * ticks_host: HOST int32 table of T + 1 entries, the tick of every column boundary (time_to_tick(k / fs)); it must start at >= 0, rise by at
+ *   least 2 from entry to entry (the column order is then the tick order; true for fs <= 220) and stay below 2^21: a table that does not is
+ *   refused with RGM_ERR_INVALID before any launch.  It is copied to the device on `stream` and must stay unchanged until that copy has run.
+ * Two calls with one host read of the sizes between them, sharing a workspace the caller leaves untouched in between:
+ *   rgm_midi_measure: counts (N,4) int64 = notes, CC events, messages of the whole file (both tracks, end-of-tracks included), file bytes.
+ *   rgm_midi_emit: note_off / cc_off / byte_off (N) int64: where sample n's rows and bytes begin in the packed arrays (exclusive sums of
+ *     the counts); notes (rows of 4 int32: pitch, velocity, start column, end column, ordered by (pitch, start column); a run that reaches
+ *     the right edge ends in column T, a note started by an onset one column behind its run has end == start), ccs (rows of 2 int32: column,
+ *     value of controller 64, in column order), bytes (the files, back to back).  *_cap: rows / bytes the arrays hold; a sample that would
+ *     not fit is left out whole.  notes / ccs may be NULL with a capacity of 0.  program: 0 .. 127.
+ * ws: rgm_midi_workspace(N, T) bytes (0 for sizes out of range), 8-byte aligned; RGM_ERR_WORKSPACE if short.  Three + two launches, no
+ * atomics, no floating point: bitwise repeatable, a sample's rows and bytes independent of N and its place in the batch. */
+size_t rgm_midi_workspace(int N, int T);
+int rgm_midi_measure(const uint8_t* roll, long long stride_n, long long stride_c, long long stride_p, long long stride_t, int N, int C,
+                     int T, int first_column_onsets, const int32_t* ticks_host, int64_t* counts, void* ws, size_t ws_bytes, void* stream);
+int rgm_midi_emit(int N, int T, int program, const int64_t* note_off, const int64_t* cc_off, const int64_t* byte_off, int32_t* notes,
+                  long long notes_cap, int32_t* ccs, long long ccs_cap, uint8_t* bytes, long long bytes_cap, void* ws, size_t ws_bytes,
+                  void* stream);
 /* The set-level half of mgeval                           music_evaluation/music_evaluator.py:117-186, mgeval/utils.py (c_dist, kl_dist,
  * overlap_area), csrc/sets.hip; definition, quirks and measurements in docs/rounds/sets.md.  Everything is float64 on `stream` in the
  * caller's workspace (8-byte aligned), no host sync, no atomics, no FMA contraction; every sum has one owner and a fixed order and the

@@ -15,13 +15,18 @@
 // five columns is evaluated, not tabulated.  No floating-point atomics: every float has one owner and a fixed summation order (lane
 // partial sums, a fixed shuffle tree, rows in order), so the answer is bitwise repeatable and a sample's numbers depend neither on N nor
 // on its row.  The input is read-only; everything runs on the caller's stream in the caller's workspace.
-#include "common.h"
+#include "roll_bits.h"
 
 #pragma clang fp contract(off)
 
 namespace rgm {
 namespace notes {
-constexpr int MIN_PIANO = 21, MAX_PIANO = 108, MAX_T = 32768, MAX_WORDS = MAX_T / 64 + 1;
+using rollbits::MAX_PIANO;
+using rollbits::MAX_T;
+using rollbits::MAX_WORDS;
+using rollbits::MIN_PIANO;
+using rollbits::n_words;
+using rollbits::top_bit;
 constexpr int N_INT = 148, N_REAL = 16, TILE = 256, HALO = 5, PEDAL_THREADS = 1024;
 
 struct RowStats {                                       // what launch 2 leaves per pitch row
@@ -34,7 +39,6 @@ struct Head {                                           // what launch 1 leaves 
 };
 
 // workspace of one sample: Head | down[nw] head[nw] shift[nw] | RowStats[128] | bits[128][3][nw]   (nw words of 64 columns 0..T)
-__host__ __device__ inline int n_words(int T) { return T / 64 + 1; }
 __host__ __device__ inline size_t sample_bytes(int T) {
   return sizeof(Head) + (size_t)3 * n_words(T) * 8 + 128 * sizeof(RowStats) + (size_t)128 * 3 * n_words(T) * 8;
 }
@@ -57,7 +61,6 @@ __device__ __forceinline__ View view(void* ws, int n, int T) {
 }
 
 __device__ __forceinline__ int column_of(int k) { return (int)(((double)k / 100.0) * 100.0); }   // int(fs * (k / fs)): k or k - 1
-__device__ __forceinline__ int top_bit(uint64_t m) { return 63 - __builtin_clzll(m); }
 
 // grid N, block 1024.  Pedal value of column t: sum of the cells >= 4 of rows 21..108, floor-divided by 88; an event where it is not 0,
 // pressing at >= 64 (16..112 keep their value, > 112 is 127) and releasing below.  In the words written, bit k stands for the rebuilt
@@ -75,17 +78,7 @@ __global__ __launch_bounds__(PEDAL_THREADS) void pedal_kernel(const uint8_t* __r
   for (int tb = 0; tb < nw * 64; tb += PEDAL_THREADS) {  // uniform trip count: every lane votes
     const int t = tb + tid;
     int sum = 0;
-    if (t < T) {
-#pragma unroll 7
-      for (int p = 0; p < MIN_PIANO; ++p) bg = max(bg, (int)vel[p * sp + t * st]);
-      if (C >= 2) {
-#pragma unroll 8
-        for (int p = MIN_PIANO; p <= MAX_PIANO; ++p) {
-          const int x = ped[p * sp + t * st];
-          sum += x >= 4 ? x : 0;
-        }
-      }
-    }
+    if (t < T) sum = rollbits::column_levels(vel, ped, sp, st, C, t, bg);
     const int val = sum / (MAX_PIANO - MIN_PIANO + 1);
     if (val != 0) last = t;
     const uint64_t hi = __ballot(val >= 64), lo = __ballot(val != 0 && val < 64), sh = __ballot(column_of(t) != t);

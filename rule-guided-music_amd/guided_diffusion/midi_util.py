@@ -104,17 +104,68 @@ def register_midi_writer(fn):
     _MIDI_WRITER = fn
 
 
-def save_piano_roll_midi(sample, save_dir, fs=100, y=None, save_piano_roll=False, save_ind=0):
+MIDI_BACKENDS = ("host", "device")
+MIDI_MAX_T = 32768
+_TICK_TABLES = {}
+
+
+def midi_tick_table(T, fs=100):
+    """The MIDI tick of every column boundary 0 .. T of a roll at fs columns per second: int32 (T + 1,), entry k =
+    SimpleMIDI.time_to_tick(k / fs) -- the host writer's own conversion, Python's half-to-even round included, so the kernels of
+    csrc/midi.hip never form a time.  Cached per (T, fs), read-only.  The device path needs a table that rises by at least 2 from entry to
+    entry (the column order is then the tick order, and the extra off of a zero-length note, one tick behind its on, falls before the next
+    column): 440 / fs >= 2, i.e. fs <= 220.  Any other fs raises ValueError.  Runs on the host."""
+    from music_rule_guidance.piano_roll_to_chord import SimpleMIDI
+    T = int(T)
+    if not 1 <= T <= MIDI_MAX_T:
+        raise ValueError(f"MIDI tick tables cover 1 .. {MIDI_MAX_T} columns, got {T}")
+    if not fs > 0:
+        raise ValueError(f"fs must be positive, got {fs}")
+    key = (T, fs)
+    tab = _TICK_TABLES.get(key)
+    if tab is None:
+        pm = SimpleMIDI()
+        tab = np.array([pm.time_to_tick(k / fs) for k in range(T + 1)], dtype=np.int64)
+        if int(np.diff(tab).min()) < 2 or int(tab[-1]) >= 1 << 21:
+            raise ValueError(f"the device MIDI writer needs ticks that rise by at least 2 per column and stay below 2^21: fs = {fs} gives a "
+                             f"smallest step of {int(np.diff(tab).min())} and a last tick of {int(tab[-1])} (fs <= 220 serves); use the host writer")
+        tab = np.ascontiguousarray(tab.astype(np.int32))
+        tab.setflags(write=False)
+        _TICK_TABLES[key] = tab
+    return tab
+
+
+def rolls_to_midi_bytes(roll_u8, fs=100, first_column_onsets=True, program=0):
+    """uint8 device rolls, channel-first (N, C, 128, T) or the (N, 128, T, C) tensor of decode_sample_for_midi -> a list of N `bytes`, each
+    the Standard MIDI File piano_roll_to_pretty_midi(roll).write() makes of that roll (first_column_onsets: with save_piano_roll_midi's forced
+    onsets in column 0), built by csrc/midi.hip and fetched with one device-to-host copy.  The rolls are not written to.  ValueError for an
+    fs the device path does not serve (midi_tick_table)."""
+    from music_rule_guidance import music_rules
+    ev = music_rules.midi_events_raw(roll_u8, fs=fs, first_column_onsets=first_column_onsets, program=program)
+    blob = ev["bytes"].cpu().numpy().tobytes()
+    ends = np.cumsum(ev["sizes_host"][:, 3])
+    return [blob[int(e - s):int(e)] for s, e in zip(ev["sizes_host"][:, 3], ends)]
+
+
+def save_piano_roll_midi(sample, save_dir, fs=100, y=None, save_piano_roll=False, save_ind=0, midi_bytes=None):
     """sample: (B, 3, 128, T) uint8 array (or (B,128,T) / (B,2,128,T)).  Writes sample_<i>[_y_<label>].midi per sample (names
     and event extraction as in the reference :67-93, incl. the forced onsets in the first column) plus the raw roll as
-    .npy; register_midi_writer replaces the built-in SMF writer.  save_piano_roll (PNG plots) is not provided."""
+    .npy; register_midi_writer replaces the built-in SMF writer.  save_piano_roll (PNG plots) is not provided.
+    midi_bytes: a list of B finished files (rolls_to_midi_bytes of the same rolls while they were on the device) to write instead of running
+    the host extraction; a registered writer still takes precedence."""
     from music_rule_guidance.piano_roll_to_chord import piano_roll_to_pretty_midi
+    if midi_bytes is not None and len(midi_bytes) != sample.shape[0]:
+        raise ValueError(f"midi_bytes holds {len(midi_bytes)} files for {sample.shape[0]} rolls")
     os.makedirs(save_dir, exist_ok=True)
     for i in range(sample.shape[0]):
         stem = f"sample_{i + save_ind}" + (f"_y_{int(y[i])}" if y is not None else "")
         np.save(os.path.join(save_dir, stem + ".npy"), sample[i])
         if _MIDI_WRITER is not None:
             _MIDI_WRITER(sample[i], os.path.join(save_dir, stem + ".midi"), fs)
+            continue
+        if midi_bytes is not None:
+            with open(os.path.join(save_dir, stem + ".midi"), "wb") as f:
+                f.write(midi_bytes[i])
             continue
         cur = np.array(sample[i])
         if cur.ndim == 3 and cur.shape[0] == 3:            # a note sounding in the first column starts there

@@ -445,6 +445,54 @@ def note_stats(roll, fs=100, first_column_onsets=False):
     return out
 
 
+# ---- note events and Standard MIDI Files of a roll on the device (docs/rounds/midi.md, csrc/midi.hip): the notes and pedal events of
+# piano_roll_to_chord.piano_roll_to_pretty_midi and the file SimpleMIDI.write makes of them, byte for byte.
+def midi_events_raw(roll, fs=100, first_column_onsets=False, program=0):
+    """uint8 device roll in either layout -> dict: counts (N, 4) int64 on the device [notes, CCs, messages, file bytes], sizes_host (the same
+    as numpy: the one host read between the two entries), note_offsets / cc_offsets / byte_offsets (N,) int64, notes (sum, 4) int32, ccs
+    (sum, 2) int32 and bytes (sum,) uint8 -- the files back to back."""
+    from guided_diffusion.midi_util import midi_tick_table
+    _rgm.require_cuda(roll)
+    if roll.dtype != torch.uint8:
+        raise ValueError(f"the MIDI kernels read uint8 rolls, got {roll.dtype}")
+    roll, N, Cc, T, strides = _note_stats_layout(roll)
+    if not 1 <= T <= NOTE_STATS_MAX_T:
+        raise ValueError(f"the MIDI kernels take 1 .. {NOTE_STATS_MAX_T} columns, got {T}")
+    if N == 0 or min(strides) <= 0:
+        raise ValueError("the MIDI kernels need a non-empty roll with positive strides")
+    ticks = midi_tick_table(T, fs)                      # ValueError for an fs the device path does not serve
+    dev = roll.device
+    counts = torch.empty((N, 4), dtype=torch.int64, device=dev)
+    with torch.cuda.device(dev):
+        nbytes = _rgm.lib.rgm_midi_workspace(N, T)
+        ws = torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=dev)
+        stream = _rgm.current_stream()
+        _rgm.check(_rgm.lib.rgm_midi_measure(ctypes.c_void_p(roll.data_ptr()), *[int(x) for x in strides], N, Cc, T, int(bool(first_column_onsets)),
+                                             ctypes.c_void_p(ticks.ctypes.data), _rgm.ptr(counts), _rgm.ptr(ws), ws.numel() * 8, stream))
+        offsets = (torch.cumsum(counts, 0) - counts).t().contiguous()          # exclusive, on the device: (4, N)
+        sizes = counts.cpu().numpy()                                            # the one host read: N sizes
+        total = sizes.sum(0)
+        notes = torch.empty((int(total[0]), 4), dtype=torch.int32, device=dev)
+        ccs = torch.empty((int(total[1]), 2), dtype=torch.int32, device=dev)
+        blob = torch.empty(int(total[3]), dtype=torch.uint8, device=dev)
+        _rgm.check(_rgm.lib.rgm_midi_emit(N, T, int(program), _rgm.ptr(offsets[0]), _rgm.ptr(offsets[1]), _rgm.ptr(offsets[3]),
+                                          _rgm.ptr(notes) if notes.numel() else None, notes.shape[0], _rgm.ptr(ccs) if ccs.numel() else None,
+                                          ccs.shape[0], _rgm.ptr(blob), blob.numel(), _rgm.ptr(ws), ws.numel() * 8, stream))
+    return {"counts": counts, "sizes_host": sizes, "note_offsets": offsets[0], "cc_offsets": offsets[1], "byte_offsets": offsets[3],
+            "notes": notes, "ccs": ccs, "bytes": blob}
+
+
+def note_events(roll, fs=100, first_column_onsets=False):
+    """The notes and sustain-pedal events piano_roll_to_pretty_midi finds in a batch of uint8 device rolls (channel-first (N, C, 128, T) or
+    the (N, 128, T, C) tensor of decode_sample_for_midi, read in place and not written to), as device tensors: n_notes, n_ccs (N,) int64;
+    notes (sum, 4) int32 rows (pitch, velocity, start column, end column) per sample in (pitch, start column) order; ccs (sum, 2) int32 rows
+    (column, value of controller 64) in column order; note_offsets, cc_offsets (N,) int64: where each sample's rows begin.  Times are
+    column / fs; fs only has to be one the device path serves (midi_util.midi_tick_table)."""
+    ev = midi_events_raw(roll, fs=fs, first_column_onsets=first_column_onsets)
+    return {"n_notes": ev["counts"][:, 0], "n_ccs": ev["counts"][:, 1], "notes": ev["notes"], "ccs": ev["ccs"],
+            "note_offsets": ev["note_offsets"], "cc_offsets": ev["cc_offsets"]}
+
+
 NOTE_STAT_RULES = {"mg_used_pitch": "total_used_pitch", "mg_pitch_range": "pitch_range", "mg_avg_ioi": "avg_IOI",
                    "mg_mean_velocity": "mean_note_velocity", "mg_mean_duration": "mean_note_duration",
                    "mg_notes_per_second": "note_density_mgeval", "mg_pitch_class_hist": "total_pitch_class_histogram",

@@ -78,6 +78,9 @@ def _load():
         "rgm_note_stats_workspace": (sz, [i32, i32]),
         "rgm_note_stats": (C.c_int, [vp] + [C.c_longlong] * 4 + [i32, i32, i32, i32, vp, vp, vp, sz, vp]),
         "rgm_roll_to_u8": (C.c_int, [vp, vp, i32, i32, i32, vp]),
+        "rgm_midi_workspace": (sz, [i32, i32]),
+        "rgm_midi_measure": (C.c_int, [vp] + [C.c_longlong] * 4 + [i32, i32, i32, i32, vp, vp, vp, sz, vp]),
+        "rgm_midi_emit": (C.c_int, [i32, i32, i32, vp, vp, vp, vp, C.c_longlong, vp, C.c_longlong, vp, C.c_longlong, vp, sz, vp]),
         "rgm_set_distances": (C.c_int, [vp, i32, vp, i32, i32, i32, vp, vp]),
         "rgm_kde_pdf_workspace": (sz, [i32, i32]),
         "rgm_kde_pdf": (C.c_int, [vp, i32, vp, i32, vp, vp, sz, vp]),

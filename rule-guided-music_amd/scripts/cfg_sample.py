@@ -30,7 +30,11 @@ from load_utils import load_model  # noqa: E402
 
 
 def main(argv=None):
-    args = create_argparser().parse_args(argv)
+    parser = create_argparser()
+    parser.add_argument("--midi_backend", default="host", choices=list(midi_util.MIDI_BACKENDS),
+                        help="'host': rank 0 extracts and writes the files one sample after the other at the end; 'device': rank 0 forms the "
+                             "same bytes with csrc/midi.hip on the gathered device rolls of every round (docs/rounds/midi.md)")
+    args = parser.parse_args(argv)
     from rgm import native as _native
     _native.set_gemm_precision(args.gemm_precision)
     comm = dist_util.setup_dist(port=args.port)
@@ -75,12 +79,18 @@ def main(argv=None):
     sample_fn = diffusion.p_sample_loop if not args.use_ddim else diffusion.ddim_sample_loop
     if args.use_dpmpp:
         sample_fn = partial(diffusion.dpmpp_sample_loop, order=int(args.dpmpp_order), eta=float(args.dpmpp_eta))
-        if rank == 0:
-            import json
-            with open(os.path.join(save_dir, "run_metadata.json"), "w") as f:
-                json.dump({"sampler": {"name": "dpmpp", "timestep_respacing": args.timestep_respacing, "steps": int(args.dpmpp_steps),
-                                       "order": int(args.dpmpp_order), "eta": float(args.dpmpp_eta)}}, f, indent=1)
-    rolls, labels = [], []
+    device_midi = args.midi_backend == "device"
+    if (args.use_dpmpp or device_midi) and rank == 0:       # a default run writes no metadata file
+        import json
+        meta = {}
+        if args.use_dpmpp:
+            meta["sampler"] = {"name": "dpmpp", "timestep_respacing": args.timestep_respacing, "steps": int(args.dpmpp_steps),
+                               "order": int(args.dpmpp_order), "eta": float(args.dpmpp_eta)}
+        if device_midi:
+            meta["midi_backend"] = "device"
+        with open(os.path.join(save_dir, "run_metadata.json"), "w") as f:
+            json.dump(meta, f, indent=1)
+    rolls, labels, midi_bytes = [], [], []
     while len(rolls) * args.batch_size < args.num_samples:
         model_kwargs = {}
         classes = None
@@ -91,13 +101,16 @@ def main(argv=None):
                            progress=args.progress)
         u8 = midi_util.decode_sample_for_midi(sample, embed_model=embed_model, scale_factor=args.scale_factor, threshold=-0.95)
         gathered, gl = gather_batch(u8, classes, world)
+        if device_midi and rank == 0:                       # every rank's rolls of this round, while they are on rank 0's device
+            for g in gathered:
+                midi_bytes.extend(midi_util.rolls_to_midi_bytes(g, fs=args.fs, first_column_onsets=True))
         rolls.extend(g.cpu().numpy() for g in gathered)
         labels.extend(g.cpu().numpy() for g in gl)
         logger.log(f"created {len(rolls) * args.batch_size} samples")
 
     arr, label_arr = assemble(rolls, labels, args.num_samples)
     if rank == 0:
-        midi_util.save_piano_roll_midi(arr, save_dir, args.fs, y=label_arr)
+        midi_util.save_piano_roll_midi(arr, save_dir, args.fs, y=label_arr, midi_bytes=midi_bytes[:len(arr)] if device_midi else None)
     if world > 1:
         dist.barrier()
     logger.log("sampling complete")

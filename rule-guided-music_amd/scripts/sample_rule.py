@@ -111,6 +111,7 @@ def write_run_metadata(save_dir, args, extra=None):
     meta["note_stats"] = bool(getattr(args, "note_stats", False))   # notes.* columns in results.csv (docs/rounds/notes.md)
     meta["long_backward"] = bool(long_backward())     # RGM_LONG_BACKWARD / set_long_backward: guidance beyond 256 / 288 tokens was allowed
     meta["particles"] = particle_metadata(args)       # --particles: the particle loop in place of the SCG search (docs/rounds/particles.md)
+    meta["midi_backend"] = getattr(args, "midi_backend", "host")    # who wrote the .midi files: the host loop or csrc/midi.hip (docs/rounds/midi.md)
     meta.update(extra or {})
     with open(os.path.join(save_dir, "run_metadata.json"), "w") as f:
         json.dump(meta, f, indent=1)
@@ -130,6 +131,14 @@ def note_stats_columns(sample_u8, t0=None, t1=None):
     cols["notes.total_pitch_class_histogram"] = st["total_pitch_class_histogram"].cpu().tolist()
     cols["notes.pitch_class_transition_matrix"] = st["pitch_class_transition_matrix"].cpu().tolist()
     return cols
+
+
+def device_midi_bytes(sample_u8, args):
+    """--midi_backend device: the finished files of the uint8 rolls decode_sample_for_midi returns, formed on the device before the rolls
+    are copied down (first-column onsets set, as save_piano_roll_midi sets them); None under the host backend."""
+    if getattr(args, "midi_backend", "host") != "device":
+        return None
+    return midi_util.rolls_to_midi_bytes(sample_u8, fs=args.fs, first_column_onsets=True)
 
 
 def summary_columns(all_results):
@@ -357,7 +366,7 @@ def build_pipeline(args, config, device):
 
 
 def main(argv=None):
-    args = add_particle_arguments(add_note_stats_arguments(add_sampler_arguments(create_argparser()))).parse_args(argv)
+    args = add_midi_arguments(add_particle_arguments(add_note_stats_arguments(add_sampler_arguments(create_argparser())))).parse_args(argv)
     args.dir = output_dir_for(args.config_path, args.class_label)
     from rgm import native as _native
     _native.set_gemm_precision(args.gemm_precision)      # "bf16x3_presplit" / "bf16x3" (fast, fp32-grade) or "fp32" (exact fp32 MFMA)
@@ -422,10 +431,11 @@ def main(argv=None):
                 KEEP_FLOAT_ROLLS.append(_decode(sample, embed_model, scale_factor=args.scale_factor).float().cpu().numpy())
         sample = midi_util.decode_sample_for_midi(sample, embed_model=embed_model, scale_factor=args.scale_factor, threshold=-0.95)
         note_cols = note_stats_columns(sample) if args.note_stats else {}                  # on the device, before the roll leaves it
+        midi_bytes = device_midi_bytes(sample, args) if args.save_files and rank0 else None
         arr = sample.cpu().numpy().transpose(0, 3, 1, 2)                                   # (B, 3, 128, T) uint8
         if args.save_files and rank0:
             midi_util.save_piano_roll_midi(arr, save_dir, args.fs, y=classes_of.cpu().numpy() if classes_of is not None else None,
-                                           save_ind=count_samples * (arr.shape[0] // args.batch_size))
+                                           save_ind=count_samples * (arr.shape[0] // args.batch_size), midi_bytes=midi_bytes)
         generated = th.from_numpy(arr.astype(np.float32)) / 63.5 - 1
         results = midi_util.eval_rule_loss(generated, rules_of)
         for name, col in list(note_cols.items()) + list(particle_cols.items()):
@@ -492,6 +502,16 @@ def add_note_stats_arguments(parser):
                    help="True: mgeval's note statistics of every saved roll (used pitches, pitch range, average IOI, pitch-class histogram, "
                         "mean velocity / duration, notes per second, transition matrix) as notes.* columns of results.csv, their means in "
                         "summary.csv; computed on the device (docs/rounds/notes.md)")
+    return parser
+
+
+def add_midi_arguments(parser):
+    """--midi_backend: who turns the final rolls into .midi files, shared by sample_rule.py, edit.py and cfg_sample.py (kept out of
+    create_argparser's defaults like the groups above; docs/rounds/midi.md)."""
+    g = parser.add_argument_group("MIDI writer")
+    g.add_argument("--midi_backend", default="host", choices=list(midi_util.MIDI_BACKENDS),
+                   help="'host': piano_roll_to_pretty_midi and SimpleMIDI.write, one sample after the other; 'device': the same bytes formed by "
+                        "csrc/midi.hip for the whole batch while the rolls are still on the device (fs <= 220)")
     return parser
 
 

@@ -416,6 +416,32 @@ int rgm_midi_measure(const uint8_t* roll, long long stride_n, long long stride_c
 int rgm_midi_emit(int N, int T, int program, const int64_t* note_off, const int64_t* cc_off, const int64_t* byte_off, int32_t* notes,
                   long long notes_cap, int32_t* ccs, long long ccs_cap, uint8_t* bytes, long long bytes_cap, void* ws, size_t ws_bytes,
                   void* stream);
+/* Standard MIDI Files read on the device                  music_rule_guidance/piano_roll_to_chord.py (SimpleMIDI._read, midi_to_full_piano_roll),
+ * the reference's datasets/piano_roll_all.py and scripts/edit.py:170-171; csrc/midi_read.hip, docs/rounds/midi_read.md.  The definition is the
+ * host reader, mirrored byte for byte; its parse step has no reference of its own (mido), its roll builder is pinned to the reference's fork.
+ * blob: the N files back to back, 16-byte aligned, its allocation padded to a multiple of 16 bytes; never written.  offsets: N + 1 int64 on the
+ *   device, offsets[N] == total_bytes.  total_tracks: the sum of the track counts of the headers (bytes 10..11) of all files of at least 14
+ *   bytes that begin with "MThd"; a file whose tracks the total does not cover gets status 9.
+ * rgm_midi_read_scan: status (N) int32, counts (N,4) int64 = notes, control changes, tempo entries (the initial one included), instruments,
+ *   columns (N) int64 = the T of the host's roll at fs.  Optional: note_off / cc_off (N + 1) int64, the exclusive row offsets over the files;
+ *   notes (rows of 8 int64: instrument, channel, pitch, velocity, start tick, end tick, and the BITS of two float64, start and end in
+ *   seconds) in (instrument, order of the note-offs) order; ccs (rows of 5 int64: instrument, number, value, tick, bits of the float64
+ *   seconds) in (instrument, event) order.  notes and ccs come together; a file whose rows do not fit the capacities is left out whole.
+ * rgm_midi_read_rolls (after a scan with the same N, total_bytes, total_tracks, fs and workspace): out (N,3,128,T) = columns [start_column,
+ *   start_column + T) of every accepted file's [velocity | onset | pedal] roll, zero beyond the file's own columns and for a refused file;
+ *   out_u8 = 0: float32, the host's values; 1: uint8 saturating at 255 with overflow (N) int64 = the number of saturated cells.
+ * status: 0 accepted, 1 not a Standard MIDI File, 2 SMPTE or zero division, 3 bad or overrunning track chunk, 4 data ending inside a message,
+ *   5 a data byte >= 0x80 in a channel message, 6 more than 2048 tempo entries, 7 no note reaching the first column, 8 a tick >= 2^40 or
+ *   2^31 columns, 9 total_tracks too small.  A refused file has zero counts and columns.
+ * ws: rgm_midi_read_workspace(N, total_bytes, total_tracks) bytes (0 for sizes out of range: N 1 .. 65535, 1 .. 2^30 bytes, 0 .. 2^26 tracks),
+ *   16-byte aligned; RGM_ERR_WORKSPACE if short; RGM_ERR_INVALID for fs <= 0, sizes or pointers, before any launch.  Float64 without
+ *   contraction, integer atomics only: bitwise repeatable, a file's results independent of N and of its place in the blob. */
+size_t rgm_midi_read_workspace(int N, long long total_bytes, int total_tracks);
+int rgm_midi_read_scan(const uint8_t* blob, const int64_t* offsets, int N, long long total_bytes, int total_tracks, double fs, int32_t* status,
+                       int64_t* counts, int64_t* columns, int64_t* note_off, int64_t* cc_off, int64_t* notes, long long notes_cap, int64_t* ccs,
+                       long long ccs_cap, void* ws, size_t ws_bytes, void* stream);
+int rgm_midi_read_rolls(int N, long long total_bytes, int total_tracks, double fs, long long start_column, int T, int out_u8, void* out,
+                        int64_t* overflow, void* ws, size_t ws_bytes, void* stream);
 /* The set-level half of mgeval                           music_evaluation/music_evaluator.py:117-186, mgeval/utils.py (c_dist, kl_dist,
  * overlap_area), csrc/sets.hip; definition, quirks and measurements in docs/rounds/sets.md.  Everything is float64 on `stream` in the
  * caller's workspace (8-byte aligned), no host sync, no atomics, no FMA contraction; every sum has one owner and a fixed order and the

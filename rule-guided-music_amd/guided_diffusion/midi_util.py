@@ -147,6 +147,127 @@ def rolls_to_midi_bytes(roll_u8, fs=100, first_column_onsets=True, program=0):
     return [blob[int(e - s):int(e)] for s, e in zip(ev["sizes_host"][:, 3], ends)]
 
 
+MIDI_READERS = ("host", "device")
+MIDI_READ_STATUS = {0: "accepted", 1: "not a Standard MIDI File", 2: "SMPTE or zero time division", 3: "bad or overrunning track chunk",
+                    4: "data ends inside a message", 5: "data byte >= 0x80 in a channel message", 6: "more than 2048 tempo entries",
+                    7: "no note reaches the first column", 8: "a tick beyond 2^40 or more than 2^31 columns", 9: "track table too small"}
+MIDI_READ_MAX_FILES = 65535
+MIDI_READ_MAX_BYTES = 1 << 30
+
+
+def pack_midi_files(files):
+    """Paths or `bytes` -> (blob, offsets, total_tracks) on the host: the files back to back in a uint8 array whose length is padded with
+    zeros to a multiple of 16 (plus 16) so that a 16-byte load of any file byte stays inside it, N + 1 int64 offsets, and the sum of the
+    track counts of the 14-byte headers that begin with MThd -- what sizes the workspace of csrc/midi_read.hip.  Runs on the host."""
+    datas = []
+    for f in files:
+        if isinstance(f, (bytes, bytearray, memoryview)):
+            datas.append(bytes(f))
+        else:
+            with open(f, "rb") as fh:
+                datas.append(fh.read())
+    if not 1 <= len(datas) <= MIDI_READ_MAX_FILES:
+        raise ValueError(f"the device MIDI reader takes 1 .. {MIDI_READ_MAX_FILES} files per call, got {len(datas)}")
+    offsets = np.zeros(len(datas) + 1, dtype=np.int64)
+    offsets[1:] = np.cumsum([len(d) for d in datas])
+    total = int(offsets[-1])
+    if not 1 <= total <= MIDI_READ_MAX_BYTES:
+        raise ValueError(f"the device MIDI reader takes 1 .. 2^30 bytes per call, got {total}")
+    blob = np.zeros((total + 15) // 16 * 16 + 16, dtype=np.uint8)
+    blob[:total] = np.frombuffer(b"".join(datas), dtype=np.uint8)
+    tracks = sum(int.from_bytes(d[10:12], "big") for d in datas if len(d) >= 14 and d[:4] == b"MThd")
+    return blob, offsets, tracks
+
+
+def _midi_read_scan(files, fs, want_events):
+    """Pack, upload and scan: the tensors both public readers share.  One host-to-device copy of the blob, one of the offsets."""
+    if not fs > 0:
+        raise ValueError(f"fs must be positive, got {fs}")
+    blob_h, offsets_h, tracks = pack_midi_files(files)
+    N, total = len(offsets_h) - 1, int(offsets_h[-1])
+    dev = torch.device("cuda", torch.cuda.current_device())
+    blob = torch.from_numpy(blob_h).to(dev)
+    offsets = torch.from_numpy(offsets_h).to(dev)
+    r = {"N": N, "total": total, "tracks": tracks, "blob": blob, "offsets": offsets,
+         "status": torch.empty(N, dtype=torch.int32, device=dev), "counts": torch.empty((N, 4), dtype=torch.int64, device=dev),
+         "columns": torch.empty(N, dtype=torch.int64, device=dev)}
+    notes = ccs = note_off = cc_off = None
+    if want_events:                                      # rows bounded by bytes: no host read before the arrays exist
+        notes = torch.zeros((total // 6 + 1, 8), dtype=torch.int64, device=dev)
+        ccs = torch.zeros((total // 3 + 1, 5), dtype=torch.int64, device=dev)
+        note_off = torch.empty(N + 1, dtype=torch.int64, device=dev)
+        cc_off = torch.empty(N + 1, dtype=torch.int64, device=dev)
+    with torch.cuda.device(dev):
+        nbytes = _rgm.lib.rgm_midi_read_workspace(N, total, tracks)
+        if nbytes == 0:
+            raise ValueError(f"the device MIDI reader does not serve {N} files of {total} bytes with {tracks} tracks")
+        ws = torch.empty((nbytes + 15) // 16 * 2, dtype=torch.int64, device=dev)
+        _rgm.check(_rgm.lib.rgm_midi_read_scan(_rgm.ptr(blob), _rgm.ptr(offsets), N, total, tracks, float(fs), _rgm.ptr(r["status"]),
+                                               _rgm.ptr(r["counts"]), _rgm.ptr(r["columns"]), _rgm.ptr(note_off), _rgm.ptr(cc_off),
+                                               _rgm.ptr(notes), 0 if notes is None else notes.shape[0], _rgm.ptr(ccs),
+                                               0 if ccs is None else ccs.shape[0], _rgm.ptr(ws), ws.numel() * 8, _rgm.current_stream()))
+    r.update(ws=ws, notes=notes, ccs=ccs, note_offsets=note_off, cc_offsets=cc_off)
+    return r
+
+
+def _midi_file_name(files, i):
+    return f"file {i}" if isinstance(files[i], (bytes, bytearray, memoryview)) else str(files[i])
+
+
+def midi_files_to_rolls(files, fs=100, columns=None, start_column=0, dtype=torch.uint8, strict=True):
+    """A batch of Standard MIDI Files (paths or `bytes`) -> device tensors {"roll" (N, 3, 128, T) [velocity | onset | pedal], "columns" (N,)
+    int64: every file's own length in columns, "status" (N,) int32 (MIDI_READ_STATUS), "overflow" (N,) int64}: what
+    midi_to_full_piano_roll(SimpleMIDI(file), fs) gives, cut to columns [start_column, start_column + T) and zero beyond the file's own end,
+    built by csrc/midi_read.hip.  dtype torch.float32: the host's values exactly; torch.uint8: saturating at 255 (the host's velocity sum of
+    overlapping notes is unclipped), `overflow` counting the saturated cells.  columns=None: T is the batch maximum (at least 1) -- the one
+    host read, of N sizes.  strict: ValueError naming the first refused file and its status; otherwise a refused file has a zero roll."""
+    if dtype not in (torch.uint8, torch.float32):
+        raise ValueError(f"rolls come as torch.uint8 or torch.float32, got {dtype}")
+    if start_column < 0 or (columns is not None and columns < 1):
+        raise ValueError(f"a window needs start_column >= 0 and columns >= 1, got {start_column} and {columns}")
+    files = list(files)
+    r = _midi_read_scan(files, fs, False)
+    if strict:
+        bad = torch.nonzero(r["status"]).flatten().cpu().numpy()
+        if len(bad):
+            code = int(r["status"][int(bad[0])])
+            raise ValueError(f"{_midi_file_name(files, int(bad[0]))}: refused by the device MIDI reader, status {code} ({MIDI_READ_STATUS[code]})")
+    T = int(columns) if columns is not None else max(1, int(r["columns"].max()) - int(start_column))
+    dev = r["blob"].device
+    roll = torch.empty((r["N"], 3, 128, T), dtype=dtype, device=dev)
+    overflow = torch.zeros(r["N"], dtype=torch.int64, device=dev)
+    with torch.cuda.device(dev):
+        _rgm.check(_rgm.lib.rgm_midi_read_rolls(r["N"], r["total"], r["tracks"], float(fs), int(start_column), T, int(dtype == torch.uint8),
+                                                _rgm.ptr(roll), _rgm.ptr(overflow), _rgm.ptr(r["ws"]), r["ws"].numel() * 8, _rgm.current_stream()))
+    return {"roll": roll, "columns": r["columns"], "status": r["status"], "overflow": overflow}
+
+
+def midi_files_to_events(files, fs=100):
+    """A batch of Standard MIDI Files -> device tensors: status (N,) int32, counts (N, 4) int64 [notes, control changes, tempo entries,
+    instruments], columns (N,) int64; notes (sum, 6) int64 rows (instrument, channel, pitch, velocity, start tick, end tick) with note_times
+    (sum, 2) float64 (start, end in seconds), in (instrument, order of the note-offs) order; ccs (sum, 4) int64 rows (instrument, number, value,
+    tick) with cc_times (sum,) float64, in (instrument, event) order; note_offsets, cc_offsets (N + 1,) int64.  What SimpleMIDI(file) holds;
+    a refused file has no rows.  One host read of the two totals trims the arrays."""
+    files = list(files)
+    r = _midi_read_scan(files, fs, True)
+    n, c = int(r["note_offsets"][-1]), int(r["cc_offsets"][-1])
+    notes, ccs = r["notes"][:n], r["ccs"][:c]
+    return {"status": r["status"], "counts": r["counts"], "columns": r["columns"], "notes": notes[:, :6].contiguous(),
+            "note_times": notes[:, 6:8].contiguous().view(torch.float64), "ccs": ccs[:, :4].contiguous(),
+            "cc_times": ccs[:, 4].contiguous().view(torch.float64), "note_offsets": r["note_offsets"], "cc_offsets": r["cc_offsets"]}
+
+
+def read_midi_piano_roll_device(path, fs=100, columns=None):
+    """read_midi_piano_roll's device counterpart for one file: the float32 (3, 128, T) roll as a device tensor (T = the file's own length, or
+    the first `columns` columns, zero-padded); a registered reader still wins, as everywhere."""
+    if _MIDI_READER is not None:
+        roll = torch.from_numpy(np.asarray(_MIDI_READER(path, fs), dtype=np.float32)).cuda()
+        if columns is not None:
+            roll = torch.nn.functional.pad(roll[:, :, :columns], (0, max(0, columns - roll.shape[2])))
+        return roll
+    return midi_files_to_rolls([path], fs=fs, columns=columns, dtype=torch.float32)["roll"][0]
+
+
 def save_piano_roll_midi(sample, save_dir, fs=100, y=None, save_piano_roll=False, save_ind=0, midi_bytes=None):
     """sample: (B, 3, 128, T) uint8 array (or (B,128,T) / (B,2,128,T)).  Writes sample_<i>[_y_<label>].midi per sample (names
     and event extraction as in the reference :67-93, incl. the forced onsets in the first column) plus the raw roll as

@@ -81,6 +81,9 @@ def _load():
         "rgm_midi_workspace": (sz, [i32, i32]),
         "rgm_midi_measure": (C.c_int, [vp] + [C.c_longlong] * 4 + [i32, i32, i32, i32, vp, vp, vp, sz, vp]),
         "rgm_midi_emit": (C.c_int, [i32, i32, i32, vp, vp, vp, vp, C.c_longlong, vp, C.c_longlong, vp, C.c_longlong, vp, sz, vp]),
+        "rgm_midi_read_workspace": (sz, [i32, C.c_longlong, i32]),
+        "rgm_midi_read_scan": (C.c_int, [vp, vp, i32, C.c_longlong, i32, C.c_double, vp, vp, vp, vp, vp, vp, C.c_longlong, vp, C.c_longlong, vp, sz, vp]),
+        "rgm_midi_read_rolls": (C.c_int, [i32, C.c_longlong, i32, C.c_double, C.c_longlong, i32, i32, vp, vp, vp, sz, vp]),
         "rgm_set_distances": (C.c_int, [vp, i32, vp, i32, i32, i32, vp, vp]),
         "rgm_kde_pdf_workspace": (sz, [i32, i32]),
         "rgm_kde_pdf": (C.c_int, [vp, i32, vp, i32, vp, vp, sz, vp]),

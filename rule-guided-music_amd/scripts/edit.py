@@ -44,8 +44,9 @@ def synthetic_roll(seed, T):
     return th.from_numpy(r)
 
 
-def load_source(source, T, fs, device, allow_synthetic=False):
-    """-> ground-truth roll (1,3,128,T) float32 in [-1,1], right-padded with background (reference :169-174)."""
+def load_source(source, T, fs, device, allow_synthetic=False, midi_reader="host"):
+    """-> ground-truth roll (1,3,128,T) float32 in [-1,1], right-padded with background (reference :169-174).  midi_reader 'device': a MIDI
+    source's first T columns are built on the device (csrc/midi_read.hip), zero beyond the file's end -- the same values."""
     if source == "dataset":
         # the reference draws a test-set excerpt here (edit.py :140-168); the dataset loader is out of scope (SURVEY 2 row 15)
         if not allow_synthetic:
@@ -60,6 +61,12 @@ def load_source(source, T, fs, device, allow_synthetic=False):
         if a.dtype == np.uint8:                         # (128,T,3) as written by decode_sample_for_midi
             a = a.transpose(2, 0, 1).astype(np.float32) / 63.5 - 1
         gt = th.from_numpy(np.ascontiguousarray(a, dtype=np.float32))[None]
+    elif midi_reader == "device":
+        with th.cuda.device(device):
+            roll = midi_util.read_midi_piano_roll_device(source, fs, columns=T)[None]
+        # the scaling stays where the host path has it: a device division by a scalar multiplies by the reciprocal, which moves values by
+        # one ulp and some of them across the truncating cast of the saved gt roll
+        return (roll.cpu() / 63.5 - 1).to(device)
     else:
         gt = th.from_numpy(midi_util.read_midi_piano_roll(source, fs)).float()[None] / 63.5 - 1
     gt = gt[..., :T]
@@ -125,7 +132,7 @@ LAST_START = None      # the start latent of the last run under --edit_start ddi
 
 
 def main(argv=None):
-    args = _sr.add_midi_arguments(create_argparser()).parse_args(argv)
+    args = _sr.add_midi_reader_arguments(_sr.add_midi_arguments(create_argparser())).parse_args(argv)
     root = "edit_demo/"
     tail = args.config_path.split("configs/")[-1] if "configs/" in args.config_path else os.path.basename(args.config_path)
     args.dir = root + os.path.splitext(tail)[0] + f"_cls_{args.class_label}"
@@ -161,10 +168,11 @@ def main(argv=None):
     if args.sampler == "dpmpp":
         edit_kwargs["noise_level"] = dpmpp_noise_level(args, config, diffusion, int(edit_kwargs["noise_level"]))
     edit_kwargs["l_start_pix"], edit_kwargs["l_end_pix"] = edit_kwargs["l_start"] * 8, edit_kwargs["l_end"] * 8
-    gt = load_source(edit_kwargs.get("source", "synthetic"), gen_shape[2] * 8, args.fs, device, allow_synthetic=args.allow_synthetic_source)
+    gt = load_source(edit_kwargs.get("source", "synthetic"), gen_shape[2] * 8, args.fs, device, allow_synthetic=args.allow_synthetic_source,
+                     midi_reader=args.midi_reader)
     if args.save_files and rank0:
         _sr.write_run_metadata(save_dir, args, {"source": edit_kwargs.get("source", "synthetic"), "source_substituted_by_synthetic": bool(substituted),
-                                                   "edit_start": args.edit_start, "noise_level": int(edit_kwargs["noise_level"])})
+                                                   "edit_start": args.edit_start, "midi_reader": args.midi_reader, "noise_level": int(edit_kwargs["noise_level"])})
     gt_latent = _encode(gt, embed_model, scale_factor=args.scale_factor)
     mask = th.ones_like(gt_latent)
     mask[:, :, edit_kwargs["l_start"]:edit_kwargs["l_end"], :] = 0.

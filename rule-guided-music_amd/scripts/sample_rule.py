@@ -515,6 +515,16 @@ def add_midi_arguments(parser):
     return parser
 
 
+def add_midi_reader_arguments(parser):
+    """--midi_reader: who turns a MIDI source into a piano roll, for edit.py and midi_to_rolls.py (kept out of create_argparser's
+    defaults and out of add_midi_arguments; docs/rounds/midi_read.md)."""
+    g = parser.add_argument_group("MIDI reader")
+    g.add_argument("--midi_reader", default="host", choices=list(midi_util.MIDI_READERS),
+                   help="'host': SimpleMIDI and midi_to_full_piano_roll, one byte, event and note after the other; 'device': the same roll "
+                        "built by csrc/midi_read.hip (a reader registered with register_midi_reader wins either way)")
+    return parser
+
+
 def add_particle_arguments(parser):
     """--particles and its options: particle rule guidance (sequential Monte Carlo) in place of the SCG search, kept out of
     create_argparser's defaults like the two groups above (docs/rounds/particles.md)."""

@@ -442,6 +442,40 @@ int rgm_midi_read_scan(const uint8_t* blob, const int64_t* offsets, int N, long 
                        long long ccs_cap, void* ws, size_t ws_bytes, void* stream);
 int rgm_midi_read_rolls(int N, long long total_bytes, int total_tracks, double fs, long long start_column, int T, int out_u8, void* out,
                         int64_t* overflow, void* ws, size_t ws_bytes, void* stream);
+/* Augmented training batches                              guided_diffusion/pr_datasets_all.py (ImageDataset.__getitem__, key_shift),
+ * train_util.py (get_kl_input), compute_std.py; csrc/augment.hip; definition, quirks and measurements in docs/rounds/augment.md.
+ *
+ * rgm_roll_augment: N uint8 excerpts (3, 128, lengths[f]) [velocity | onset | pedal] lie in `blob` at byte offsets[f] (any byte offset; the
+ *   blob itself 16-byte aligned, blob_bytes the padded allocation, a multiple of 16; offsets holds N + 1 entries, the last is not read).
+ *   params (B, 5) int32 rows (file, start, pr_len, k, flags), flags bit 0: time stretch, bit 1: key shift.  out (B, 3, 128, S) float32:
+ *   x = u8 / 63.5f - 1 of columns [start, start + pr_len) resampled to S columns (bit 0; [0, S) otherwise) -- stretched (pr_len < S:
+ *   velocity and pedal by torch's nearest map, every source onset kept once, -1 between), compressed (pr_len > S: nearest, an onset of 1.0
+ *   where the resampled velocity rises) or copied; velocity and onset rows moved by new[p] = old[(p + |k|) mod 128] (bit 1; k < 0 shifts
+ *   the same way as k > 0, the reference's behaviour); pitches < 21 and > 108 set to -1.  status (B) int32: 0 accepted, 1 file index out
+ *   of range or the file's extent outside the blob, 2 window outside the file, 3 pr_len < 1 or above rgm_roll_augment_capacity(S) =
+ *   ((S + S / 16 + 15) & ~15) + 16 source columns, 4 |k| > 127 -- checked in the order 1, 3, 2, 4; a refused row is -1 throughout, the
+ *   other rows are unaffected.  1 <= S <= 16384, 1 <= B <= 2^23.  One launch of 128 B workgroups, no atomics, the blob is only read;
+ *   every launch repeats bit for bit and a row's result depends neither on B nor on its position.  Size and pointer errors return a
+ *   status before the launch.
+ * rgm_latent_windows: moments (n_tiles * B, 8, 16, 16), tile s of sample b in row s * B + b (the encoder's output for the stacked tiles).
+ *   z[b, c, 16 s + j, i] = moments[s B + b, c, i, j] (the posterior mode, c < 4);  shift_size = 0: z0 (B, 4, 16 n_tiles, 16) = z *
+ *   scale_factor;  shift_size > 0 (n_tiles >= 8): z0[b W + w, c, r, i] = z[b, c, 16 shift_size w + r, i] * scale_factor, r < 128,
+ *   W = rgm_latent_windows_count(n_tiles, shift_size) = (16 n_tiles - 128) / (16 shift_size) + 1.  x_t (NULL: skipped), same shape:
+ *   sqrt_ac[t[row]] * z0 + sqrt_1mac[t[row]] * noise, two float32 products and a sum; t int64 per output row (clamped into the tables of
+ *   num_timesteps float32 entries); noise from the caller's buffer, or (NULL) the values rgm_randn(seed, offset) writes into a tensor of
+ *   z0's shape.  One launch.
+ * rgm_latent_std: out[3] float64 = mean, unbiased standard deviation (torch.std) and 1 / std of n float32 values: float64 sums and
+ *   sums of squares of chunks of 2048 in a fixed order, the chunks added by one wave in a fixed order.  ws: rgm_latent_std_workspace(n)
+ *   bytes, 8-byte aligned.  n = 1 gives NaN.  Two launches, no atomics, bitwise repeatable. */
+int rgm_roll_augment_capacity(int S);
+int rgm_roll_augment(const uint8_t* blob, long long blob_bytes, const int64_t* offsets, const int32_t* lengths, int N, const int32_t* params,
+                     int B, int S, float* out, int32_t* status, void* stream);
+int rgm_latent_windows_count(int n_tiles, int shift_size);
+int rgm_latent_windows(const float* moments, int B, int n_tiles, int shift_size, float scale_factor, float* z0, const int64_t* t,
+                       const float* sqrt_ac, const float* sqrt_1mac, int num_timesteps, const float* noise, uint64_t seed, uint64_t offset,
+                       float* x_t, void* stream);
+size_t rgm_latent_std_workspace(long long n);
+int rgm_latent_std(const float* x, long long n, double* out, void* ws, size_t ws_bytes, void* stream);
 /* The set-level half of mgeval                           music_evaluation/music_evaluator.py:117-186, mgeval/utils.py (c_dist, kl_dist,
  * overlap_area), csrc/sets.hip; definition, quirks and measurements in docs/rounds/sets.md.  Everything is float64 on `stream` in the
  * caller's workspace (8-byte aligned), no host sync, no atomics, no FMA contraction; every sum has one owner and a fixed order and the

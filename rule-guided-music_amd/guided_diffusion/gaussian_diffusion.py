@@ -426,6 +426,55 @@ class GaussianDiffusion:
         return (self._per_sample(self.sqrt_alphas_cumprod, t, x_start) * x_start
                 + self._per_sample(self.sqrt_one_minus_alphas_cumprod, t, x_start) * noise)
 
+    def _q_tabs(self, device):
+        """float32 device copies of sqrt_alphas_cumprod and sqrt_one_minus_alphas_cumprod: what q_sample's per-sample factors are cast to"""
+        key = "q" + str(device)
+        if key not in self._tables:
+            self._tables[key] = tuple(th.from_numpy(a).to(device=device, dtype=th.float32).contiguous()
+                                      for a in (self.sqrt_alphas_cumprod, self.sqrt_one_minus_alphas_cumprod))
+        return self._tables[key]
+
+    def noised_latents(self, moments, t, batch_size, scale_factor=1., shift_size=0, noise=None, seed=None, offset=0):
+        """The fused tail of the classifier input path (csrc/augment.hip, rgm_latent_windows): encoder moments of the stacked tiles
+        (tiles * batch_size, 8, 16, 16) -> (z0, x_t), z0 the scaled posterior mode re-assembled along time (shift_size 0) or cut into
+        windows of 128 latent rows 16 * shift_size apart, x_t = q_sample(z0, t, noise) bit for bit, in one launch.  t int64 per row of z0,
+        or None: only z0.  noise: a tensor of z0's shape, or None: the Philox stream rgm_randn(seed, offset) would write into such a tensor
+        (seed None: this object's stream, reserved like any other draw)."""
+        _rgm.require_cuda(moments, t, noise)
+        moments = moments.float().contiguous()
+        B = int(batch_size)
+        if moments.dim() != 4 or tuple(moments.shape[1:]) != (8, 16, 16) or B < 1 or moments.shape[0] % B:
+            raise ValueError(f"moments are (tiles * batch_size, 8, 16, 16), got {tuple(moments.shape)} for batch_size {batch_size}")
+        tiles = moments.shape[0] // B
+        W = int(_rgm.lib.rgm_latent_windows_count(tiles, int(shift_size)))
+        if W < 1:
+            raise ValueError(f"shift_size = {shift_size} with {tiles} tiles: a window is 128 latent rows (8 tiles)")
+        dev = moments.device
+        z0 = th.empty((B * W, 4, 128 if shift_size else 16 * tiles, 16), dtype=th.float32, device=dev)
+        x_t = sa = sb = None
+        if t is not None:
+            t = t.to(device=dev, dtype=th.int64).contiguous()
+            if tuple(t.shape) != (B * W,):
+                raise ValueError(f"t holds one step per row of z0 ({B * W}), got {tuple(t.shape)}")
+            sa, sb = self._q_tabs(dev)
+            x_t = th.empty_like(z0)
+            if noise is None and seed is None and self.noise_fn is not None:
+                noise = self._draw(z0.shape, dev)
+            if noise is not None:
+                noise = noise.float().contiguous()
+                if noise.shape != z0.shape:
+                    raise ValueError(f"noise of shape {tuple(noise.shape)} for latents {tuple(z0.shape)}")
+            elif seed is None:
+                if self.noise is None:
+                    self.noise = PhiloxNoise()
+                seed, offset = self.noise.seed, self.noise.reserve(z0.numel())
+        with th.cuda.device(dev):
+            _rgm.check(_rgm.lib.rgm_latent_windows(_rgm.ptr(moments), B, tiles, int(shift_size), float(scale_factor), _rgm.ptr(z0), _rgm.ptr(t),
+                                                   _rgm.ptr(sa), _rgm.ptr(sb), self.num_timesteps, _rgm.ptr(noise),
+                                                   C.c_uint64(int(seed or 0) & 0xFFFFFFFFFFFFFFFF), C.c_uint64(int(offset)), _rgm.ptr(x_t),
+                                                   _rgm.current_stream()))
+        return z0, x_t
+
     def q_posterior_mean_variance(self, x_start, x_t, t):
         assert x_start.shape == x_t.shape
         mean = (self._per_sample(self.posterior_mean_coef1, t, x_t) * x_start

@@ -167,6 +167,11 @@ long long rgm_gn_fallback_tiles(int reset);
  * min_batch samples take it; 0 = never; -1 (default) = the batch sizes where a same-box sweep found it ahead (2, 5..9, 17..39, 57..).
  * *prev (optional) receives the previous setting. */
 int rgm_set_dit_halves(int min_batch, int* prev);
+/* Epilogue of the 128x144 pre-split GEMM tile (tile 81: proj / fc2 of a DiT block at the samplers' batches): 0 = four consumer waves write
+ * bias / activation / gate / residual straight from their accumulators; 1 = the tile passes through the (then idle) operand ring and all
+ * eight waves move whole 576-byte rows.  Identical results.  Default: RGM_G144_EPI, else 1.  *prev (optional) receives the previous mode;
+ * another mode is RGM_ERR_INVALID and changes nothing. */
+int rgm_set_gemm144_epilogue(int mode, int* prev);
 /* Short-sequence attention of the bf16x3 modes at head_dim 72 (T <= 128: C5's half windows; ref guided_diffusion/dit.py:263-288) with TWO
  * workgroups per CU (four waves and 79 KiB of LDS each) instead of the one-per-CU guard of round 3: the guard answered a hazard of the
  * interleaved Q prologue, which the two-phase prologue removed (profiles/r05_attn_hazard_two_phase_n96.txt).  1 = on,

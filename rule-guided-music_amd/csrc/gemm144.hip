@@ -12,8 +12,10 @@
 // loader/consumer split (PIPE 4): waves 4-7 issue all LDS-DMA (36 KiB stages: 128 A rows, 144 B rows, 16 rows of padding so that
 // every loader wave owns 9 pieces), waves 0-3 multiply from registers and fetch the next tile's 22 fragments between the MFMAs of the
 // last two thirds of a tile; one barrier per K-tile.  The product is computed transposed (the B fragment is the MFMA's A operand): a lane
-// then holds FOUR CONSECUTIVE COLUMNS of one output row and the epilogue reads bias / gate / residual and writes C 16 B per lane
-// straight from the accumulators -- no pass through LDS.  Term order per accumulator: al*bh, ah*bl, ah*bh (as everywhere).
+// then holds FOUR CONSECUTIVE COLUMNS of one output row.  Epilogue (EPI 1, the default; docs/rounds/g144_epilogue.md): the accumulators
+// pass through the ring, idle by then, as a row-major fp32 image and all eight waves move whole 576-byte rows of bias / gate / residual
+// and C; EPI 0, the form it replaced and is bit-identical to: the four consumer waves write 16 B per lane straight from the accumulators
+// (64-byte segments of 16 rows per instruction).  Term order per accumulator: al*bh, ah*bl, ah*bh (as everywhere).
 #include "common.h"
 
 namespace rgm {
@@ -38,11 +40,39 @@ constexpr int ROWS = BM + BN + PAD;           // LDS rows per stage
 constexpr int STAGE = ROWS * 128;             // 36 KiB
 constexpr int LSEG = ROWS / 8 / 4;            // 1-KiB pieces per loader wave and K-tile: 9
 constexpr int TM = 2, TN = 9;                 // 16x16 accumulator tiles per consumer wave (32 rows x 144 columns)
+// EPI 1 (whole rows): the tile as a row-major fp32 image in the ring, which is dead behind the K loop.  Row stride 576 + 16 bytes = 37
+// 16-byte slots: the eight rows of a ds_write_b128 lane group (8 contiguous lanes, banks mod 32) land on eight different slots of 128 bytes
+constexpr int CHUNKS = BN / 4;                // 16-byte chunks per tile row: 36 = 576 contiguous bytes
+constexpr int EROW = BN * 4 + 16;             // bytes per row of the staged image
+constexpr int EITER = BM * CHUNKS / 512;      // chunks per lane: 9 (a wave walks 16 rows)
+constexpr int ELOADS = 3 * EITER;             // 16-byte loads per lane in front of the row walk: bias, gate row, residual of every chunk
+static_assert(BM * CHUNKS % 512 == 0 && CHUNKS % 2 == 0 && (64 * EITER) % CHUNKS == 0, "a wave owns whole rows; lane parity is chunk parity");
+
+// Four columns of one row through the epilogue -- (acc * alpha + bias), activation, (* gate + residual) -- for both forms of the epilogue.
+// Both multiply-adds are FUSED, said so (what hipcc's default contraction made of the expressions this replaces): the two forms differ in
+// code shape and must not differ in the last bit.
+__device__ __forceinline__ void epi_chunk(float (&v)[4], const f32x4& a, float alpha, const float4& b, int act, bool reads, const float4& g,
+                                          const float4& r) {
+  v[0] = __builtin_fmaf(a[0], alpha, b.x); v[1] = __builtin_fmaf(a[1], alpha, b.y);
+  v[2] = __builtin_fmaf(a[2], alpha, b.z); v[3] = __builtin_fmaf(a[3], alpha, b.w);
+  if (act == 1) {
+#pragma unroll
+    for (int e = 0; e < 4; ++e) v[e] = silu_f(v[e]);
+  } else if (act == 2) {
+#pragma unroll
+    for (int e = 0; e < 4; ++e) v[e] = gelu_tanh_fast_f(v[e]);
+  }
+  if (reads) {
+    v[0] = __builtin_fmaf(v[0], g.x, r.x); v[1] = __builtin_fmaf(v[1], g.y, r.y);
+    v[2] = __builtin_fmaf(v[2], g.z, r.z); v[3] = __builtin_fmaf(v[3], g.w, r.w);
+  }
+}
 
 // DBG: s_memtime stamps of the middle workgroup (tools/g144_stamp.py; rgm_gemm144_dbg), 8 slots per wave:
 //   consumers: 0 barrier wait (arrival -> release), 1 whole K loop, 2 prologue (entry -> K loop), 3 epilogue, 7 K-tiles
 //   loaders:   0 barrier wait, 1 whole K loop, 2 prologue, 4 piece issue, 5 landing wait, 7 K-tiles
-template <int NSTAGE, int DBG = 0, int EXP = 0, int PF = 0>
+// EPI: 0 the epilogue straight from the accumulators (consumer waves only), 1 through the ring, all eight waves moving whole rows
+template <int NSTAGE, int DBG = 0, int EXP = 0, int PF = 0, int EPI = 0>
 __global__ __launch_bounds__(512) void gemm144_kernel(GemmParams p, const char* __restrict__ zero_page, int tiles_m, int tiles_n,
                                                       long long* __restrict__ dbg = nullptr, int pf_a = 1) {
   extern __shared__ __attribute__((aligned(16))) char ring[];
@@ -75,6 +105,50 @@ __global__ __launch_bounds__(512) void gemm144_kernel(GemmParams p, const char* 
   const int KT = p.K >> 5;
   const char* Ab = reinterpret_cast<const char*>(p.A + (long long)z * p.sA);
   const char* Bb = reinterpret_cast<const char*>(p.B + (long long)z * p.sB);
+  unsigned long long t_loop = 0;
+  // ---- EPI 1: chunk it * 64 + lane of the wave's 16 rows (36 chunks of 16 bytes per row: consecutive lanes move consecutive chunks, a wave
+  // instruction 1 KiB of contiguous rows).  What a chunk reads from memory -- bias, gate row, residual -- is requested BEFORE the tile is staged:
+  // by the loaders as soon as their last piece is out, by the consumers behind their last MFMA.  Rows past M read row M - 1 (never stored).
+  float4 e_b[EITER], e_g[EITER], e_r[EITER];
+  // (the epilogue's kernel arguments are read where it begins, not here: every argument line the prologue waits for arrives cold)
+  auto epi_request = [&]() {
+    const float* resb = p.res ? p.res + (long long)z * p.sRes : nullptr;
+    const float* biasb = p.bias ? p.bias + (long long)z * p.sBias : nullptr;
+    // straight-line code (it runs once, on cold instruction lines): beside a gate or a residual an absent operand is read from the zero
+    // page, and the gate row of a
+    // chunk comes without a division per chunk -- row0 / rows_per_gate once per wave, then the step count over the wave's 16 rows: a
+    // comparison where a gate row spans 16 rows or more (at most one step), else (x + 0.5) / rows_per_gate with x < 31 through v_rcp_f32,
+    // which is at least 1 / 30 away from every integer
+    const int row0 = min(m0 + 16 * wave, p.M - 1);
+    const int rpg = p.gate ? p.rows_per_gate : 1, q0 = row0 / rpg, rem0 = row0 - q0 * rpg;
+    const float rcp = __builtin_amdgcn_rcpf((float)rpg);
+    const float* bp = biasb ? biasb : reinterpret_cast<const float*>(zero_page);
+    const float* gp = p.gate ? p.gate : reinterpret_cast<const float*>(zero_page);
+    const float* rp = resb ? resb : reinterpret_cast<const float*>(zero_page);
+    const int bm = biasb ? 1 : 0, gm = p.gate ? 1 : 0, rm = resb ? 1 : 0;      // column and row strides of an absent operand: 0
+    const long long gld = p.gate ? p.gate_ld : 0, rld = resb ? p.ldres : 0;
+    // EITER loads with a bias alone, ELOADS with a gate or a residual, none with neither (epi_loads below: the loaders count them in their
+    // vmcnt waits; every lane of the chip asking the zero page for nothing measured 2 % on the B = 4 forward, whose K slices carry no epilogue)
+    static_for<0, EITER>([&](auto ic) { e_b[decltype(ic)::value] = make_float4(0.f, 0.f, 0.f, 0.f); });
+    if (biasb || p.gate || resb) {
+      static_for<0, EITER>([&](auto ic) {
+        constexpr int it = decltype(ic)::value;
+        const int idx = it * 64 + lane;
+        e_b[it] = ldg16(bp + (n0 + 4 * (idx % CHUNKS)) * bm);
+      });
+    }
+    if (p.gate || resb) {
+      static_for<0, EITER>([&](auto ic) {
+        constexpr int it = decltype(ic)::value;
+        const int idx = it * 64 + lane, col = n0 + 4 * (idx % CHUNKS);
+        const int row = min(m0 + 16 * wave + idx / CHUNKS, p.M - 1), x = rem0 + (row - row0);
+        const int gr = q0 + (rpg >= 16 ? (x >= rpg ? 1 : 0) : (int)(((float)x + 0.5f) * rcp));
+        e_g[it] = ldg16(gp + gr * gld + col * gm);       // (absent gate: zeros here, the row walk takes 1)
+        e_r[it] = ldg16(rp + row * rld + col * rm);
+      });
+    }
+  };
+  const int epi_loads = (p.gate || p.res) ? ELOADS : p.bias ? EITER : 0;       // wave-uniform
 
   if (wave >= 4) {
     // ---- loader waves.  Piece s of a stage = LDS rows 8s..8s+7; lane = (row r8, physical 16-B chunk pc) fetches logical chunk
@@ -99,11 +173,21 @@ __global__ __launch_bounds__(512) void gemm144_kernel(GemmParams p, const char* 
         src[i] += inc[i];
       });
     };
-    auto wait_flying = [&](int tiles) {                 // wave-uniform: at most `tiles` of the newest tiles may still fly
+    // EPI 1: the wave's ELOADS epilogue loads go out right behind its LAST piece (NSTAGE - 1 K-tiles before the end: the residual rows arrive
+    // under the K loop).  They are younger than every piece and vmcnt retires in order, so from then on a wait for pieces allows ELOADS more.
+    auto wait_flying = [&](int tiles, auto rq) {        // wave-uniform: at most `tiles` of the newest tiles may still fly
       static_for<0, NSTAGE - 1>([&](auto c) {
-        if (tiles == decltype(c)::value) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(decltype(c)::value * LSEG) : "memory");
+        if (tiles == decltype(c)::value) {
+          constexpr int pieces = decltype(c)::value * LSEG;
+          if (decltype(rq)::value && epi_loads == ELOADS) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(pieces + ELOADS) : "memory");
+          else if (decltype(rq)::value && epi_loads == EITER) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(pieces + EITER) : "memory");
+          else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(pieces) : "memory");
+        }
       });
     };
+    using L0 = std::integral_constant<int, 0>;
+    using L1 = std::integral_constant<int, 1>;
+    static_assert((NSTAGE - 2) * LSEG + ELOADS <= 63, "vmcnt has six bits");
     // (Prologue, stamped in the C2 forward: ~4 k cycles until the addresses are set up -- kernel arguments and code arrive cold --, ~2.5 k for
     // the first tile's nine pieces to be issued and land, ~1 k more for the next two.  Releasing the consumers as soon as tile 0 is in, the other
     // two tiles issued behind barrier P, moved the barrier from ~8.9 k to ~7.9 k cycles and the C2 step by nothing: 11.50 / 11.48 ms over three
@@ -112,7 +196,7 @@ __global__ __launch_bounds__(512) void gemm144_kernel(GemmParams p, const char* 
     static_for<0, NSTAGE - 1>([&](auto c) {
       if (decltype(c)::value < KT) issue_tile(ring + decltype(c)::value * STAGE);
     });
-    wait_flying(min(NSTAGE - 2, KT - 1));
+    wait_flying(min(NSTAGE - 2, KT - 1), L0{});
     if (DBG) tacc[6] = now() - t_entry;                 // ... the first tiles issued, tile 0 landed
     __builtin_amdgcn_s_barrier();                       // barrier P: tile 0 is in LDS
     int s2 = NSTAGE - 1;
@@ -121,12 +205,14 @@ __global__ __launch_bounds__(512) void gemm144_kernel(GemmParams p, const char* 
       t0 = now();
       tacc[2] = t0 - t_entry;
     }
-    for (int kt = 0; kt + 1 < KT; ++kt) {
+    // one K-tile of the loop.  ISSUE: a piece set goes out (into tile kt-1's stage: every consumer read it before barrier kt-1); RQ: the
+    // epilogue's loads are out
+    auto loop_tile = [&](int kt, auto issue, auto rq) {
       unsigned long long ta = 0, tb = 0, tc = 0;
       if (DBG) ta = now();
-      if (kt + NSTAGE - 1 < KT && !(EXP & 4)) issue_tile(ring + s2 * STAGE);   // into tile kt-1's stage: every consumer read it before barrier kt-1
+      if (decltype(issue)::value && !(EXP & 4)) issue_tile(ring + s2 * STAGE);
       if (DBG) tb = now();
-      wait_flying(min(NSTAGE - 2, KT - 2 - kt));
+      wait_flying(min(NSTAGE - 2, KT - 2 - kt), rq);
       if (DBG) tc = now();
       if constexpr (!(EXP & 1)) __builtin_amdgcn_s_barrier();   // barrier kt: tile kt+1 is in LDS
       if (DBG) {
@@ -135,6 +221,14 @@ __global__ __launch_bounds__(512) void gemm144_kernel(GemmParams p, const char* 
         tacc[0] += now() - tc;
       }
       s2 = s2 == NSTAGE - 1 ? 0 : s2 + 1;
+    };
+    int kt = 0;
+    for (; kt + NSTAGE - 1 < KT; ++kt) loop_tile(kt, L1{}, L0{});      // (kt + 1 < KT as well: NSTAGE >= 2)
+    if constexpr (EPI != 0) {
+      epi_request();                                                    // once, in straight-line code behind the last piece
+      for (; kt + 1 < KT; ++kt) loop_tile(kt, L0{}, L1{});
+    } else {
+      for (; kt + 1 < KT; ++kt) loop_tile(kt, L0{}, L0{});
     }
     if (DBG) {
       tacc[1] = now() - t0;
@@ -142,9 +236,15 @@ __global__ __launch_bounds__(512) void gemm144_kernel(GemmParams p, const char* 
       if (blockIdx.x == gridDim.x / 2 && blockIdx.z == 0 && lane == 0)
         for (int i = 0; i < 8; ++i) dbg[wave * 8 + i] = (long long)tacc[i];
     }
-    return;
-  }
-
+    if constexpr (EPI == 0) return;
+    // EPI 1: every piece of this wave has landed (the loop's last wait leaves only the epilogue's loads in flight; said again, since the ring
+    // is about to be overwritten; K >= 64, so the loop ran).  Both barriers below are reached by all eight waves on every path: the loop
+    // above and the consumers' K loop hold KT - 1 barriers each, whatever KT's parity, DBG, EXP or PF.
+    wait_flying(0, L1{});
+    __builtin_amdgcn_s_barrier();                       // barrier E1: no wave reads the ring any more
+    __builtin_amdgcn_s_barrier();                       // barrier E2: the tile is staged
+    asm volatile("" ::: "memory");
+  } else {
   // ---- consumer waves
   const int l15 = lane & 15, kb = lane >> 4;
   const int rq = (l15 >> 1) & 7;                        // tile row offsets are multiples of 16
@@ -286,7 +386,6 @@ __global__ __launch_bounds__(512) void gemm144_kernel(GemmParams p, const char* 
     term(I1{}, cur, lo, cur, nullptr, I0{});
     term(I2{}, cur, lo, cur, nullptr, I0{});
   };
-  unsigned long long t_loop = 0;
   if (DBG) {
     t_loop = now();
     tacc[2] = t_loop - t_entry;
@@ -308,6 +407,7 @@ __global__ __launch_bounds__(512) void gemm144_kernel(GemmParams p, const char* 
     t_loop = t;
   }
 
+  if constexpr (EPI == 0) {
   // ---- epilogue, straight from the accumulators: acc[im][in][e] = C[m0 + arow0 + 16 im + l15][n0 + 16 in + 4 kb + e]
   float* __restrict__ Cb = p.C + (long long)z * p.sC;
   const float* resb = p.res ? p.res + (long long)z * p.sRes : nullptr;
@@ -335,19 +435,8 @@ __global__ __launch_bounds__(512) void gemm144_kernel(GemmParams p, const char* 
 #pragma unroll
     for (int in = 0; in < TN; ++in) {
       const int col = colb + in * 16;
-      float v[4] = {acc[im][in][0] * p.alpha + bv[in].x, acc[im][in][1] * p.alpha + bv[in].y, acc[im][in][2] * p.alpha + bv[in].z,
-                    acc[im][in][3] * p.alpha + bv[in].w};
-      if (p.act == 1) {
-#pragma unroll
-        for (int e = 0; e < 4; ++e) v[e] = silu_f(v[e]);
-      } else if (p.act == 2) {
-#pragma unroll
-        for (int e = 0; e < 4; ++e) v[e] = gelu_tanh_fast_f(v[e]);
-      }
-      if (reads) {
-        v[0] = v[0] * g4[in].x + r4[in].x; v[1] = v[1] * g4[in].y + r4[in].y;
-        v[2] = v[2] * g4[in].z + r4[in].z; v[3] = v[3] * g4[in].w + r4[in].w;
-      }
+      float v[4];
+      epi_chunk(v, acc[im][in], p.alpha, bv[in], p.act, reads, g4[in], r4[in]);
       if (p.out_split) {     // (before the row guard: both lanes of a pair -- same row, kb ^ 1 -- take part in the exchange)
         bf16x4 hi, lo;
 #pragma unroll
@@ -364,6 +453,52 @@ __global__ __launch_bounds__(512) void gemm144_kernel(GemmParams p, const char* 
         *reinterpret_cast<float4*>(Cb + (long long)row * p.ldc + col) = make_float4(v[0], v[1], v[2], v[3]);
       }
     }
+  }
+  } else {
+    // ---- EPI 1, staging: the raw accumulators as a row-major image over the ring.  The consumers' own L2-prefetch requests (PF) land in the
+    // scratch KiB BEHIND the ring, outside the image, and are older than the row walk's loads requested here (vmcnt retires in order: a wait for
+    // those covers them).  Barrier E1: every consumer is through its last fragment read (they end in the K-tile before the last), every
+    // loader's pieces have landed.
+    epi_request();
+    __builtin_amdgcn_s_barrier();                       // barrier E1
+#pragma unroll
+    for (int im = 0; im < TM; ++im)
+#pragma unroll
+      for (int in = 0; in < TN; ++in)
+        *reinterpret_cast<f32x4*>(ring + (arow0 + im * 16 + l15) * EROW + (in * 16 + 4 * kb) * 4) = acc[im][in];
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_s_barrier();                       // barrier E2: the tile is staged
+    asm volatile("" ::: "memory");
+  }
+  }   // consumer waves
+
+  if constexpr (EPI != 0) {
+    // ---- EPI 1, all eight waves: 16 rows per wave in 576-byte runs; the lane that read a residual chunk writes that chunk (res may be C)
+    typedef split_t bf16x4 __attribute__((ext_vector_type(4)));
+    float* __restrict__ Cb = p.C + (long long)z * p.sC;
+    const bool reads = p.gate || p.res;
+    static_for<0, EITER>([&](auto ic) {
+      constexpr int it = decltype(ic)::value;
+      const int idx = it * 64 + lane, rl = 16 * wave + idx / CHUNKS, ch = idx % CHUNKS;
+      const int row = m0 + rl, col = n0 + 4 * ch;
+      const f32x4 a = *reinterpret_cast<const f32x4*>(ring + rl * EROW + ch * 16);
+      float v[4];
+      epi_chunk(v, a, p.alpha, e_b[it], p.act, reads, p.gate ? e_g[it] : make_float4(1.f, 1.f, 1.f, 1.f), e_r[it]);
+      if (row < p.M) {       // lanes 2k, 2k + 1 hold chunks 2j, 2j + 1 of ONE row (36 chunks per row, even): a pair is in or out together
+        if (p.out_split) {
+          bf16x4 hi, lo;
+#pragma unroll
+          for (int e = 0; e < 4; ++e) {
+            hi[e] = (split_t)v[e];
+            lo[e] = (split_t)(v[e] - (float)hi[e]);
+          }
+          store_split4_maybe_pair<1>(reinterpret_cast<split_t*>(Cb + (long long)row * p.ldc), col, hi, lo);
+        } else {
+          *reinterpret_cast<float4*>(Cb + (long long)row * p.ldc + col) = make_float4(v[0], v[1], v[2], v[3]);
+        }
+      }
+    });
+    if (wave >= 4) return;
   }
   if (DBG) {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -385,6 +520,10 @@ __global__ __launch_bounds__(512) void gemm144_kernel(GemmParams p, const char* 
 constexpr size_t DBG_SLOTS = 64 + 8 * 4096;
 char* g_zero144 = nullptr;
 long long* g_dbg144 = nullptr;
+// epilogue form (rgm_set_gemm144_epilogue / RGM_G144_EPI, read once): 0 straight from the accumulators, 1 (default) whole rows through the
+// ring.  Same box, C2 step, parent / whole rows alternating: 11.21-11.38 / 11.08-11.11 ms and 10.93-11.00 / 10.86-10.93 on another box; B = 4
+// forward 4.81-4.94 / 4.77-4.79 (docs/rounds/g144_epilogue.md)
+int g_epi144 = getenv("RGM_G144_EPI") ? (atoi(getenv("RGM_G144_EPI")) == 0 ? 0 : 1) : 1;
 }  // namespace
 
 // shapes and epilogues this kernel carries (gemm2_launch asks before it picks tile 81)
@@ -413,11 +552,15 @@ int gemm144_launch(const GemmParams& p, hipStream_t s) {
     static const int fixed = getenv("RGM_G144_RASTER") ? atoi(getenv("RGM_G144_RASTER")) : 0;   // A/B runs
     pr.raster_group = fixed > 0 ? (fixed < tm ? fixed : tm) : (tm < 8 ? tm : 8);
   }
-  auto k = pf_on ? gemm144_kernel<NSTAGE, 0, 0, PFD> : gemm144_kernel<NSTAGE>;
+  const int epi = g_epi144;
+  auto k = epi ? (pf_on ? gemm144_kernel<NSTAGE, 0, 0, PFD, 1> : gemm144_kernel<NSTAGE, 0, 0, 0, 1>)
+               : (pf_on ? gemm144_kernel<NSTAGE, 0, 0, PFD> : gemm144_kernel<NSTAGE>);
   static bool attr = false;
   if (!attr) {
     RGM_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm144_kernel<NSTAGE, 0, 0, PFD>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     RGM_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm144_kernel<NSTAGE>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    RGM_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm144_kernel<NSTAGE, 0, 0, PFD, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    RGM_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm144_kernel<NSTAGE, 0, 0, 0, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     attr = true;
   }
   if (g_dbg144) {                // stamped variant (tools/g144_stamp.py)
@@ -426,15 +569,20 @@ int gemm144_launch(const GemmParams& p, hipStream_t s) {
       (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kd), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
       hipLaunchKernelGGL(kd, dim3((unsigned)(tm * tn), 1, (unsigned)p.batch), dim3(512), lds, s, pr, (const char*)g_zero144, tm, tn, g_dbg144, pf_on >> 1);
     };
-    switch (exp) {            // (with the L2 prefetch, as the product kernel runs)
-      case 1: launch_dbg(gemm144_kernel<NSTAGE, 1, 1, PFD>); break;
-      case 2: launch_dbg(gemm144_kernel<NSTAGE, 1, 2, PFD>); break;
-      case 4: launch_dbg(gemm144_kernel<NSTAGE, 1, 4, PFD>); break;
-      case 7: launch_dbg(gemm144_kernel<NSTAGE, 1, 7, PFD>); break;
-      default:
-        if (pf_on) launch_dbg(gemm144_kernel<NSTAGE, 1, 0, PFD>);
-        else launch_dbg(gemm144_kernel<NSTAGE, 1, 0>);
-    }
+    auto launch_exp = [&](auto ec) {     // in the epilogue form that is set
+      constexpr int E = decltype(ec)::value;
+      switch (exp) {            // (with the L2 prefetch, as the product kernel runs)
+        case 1: launch_dbg(gemm144_kernel<NSTAGE, 1, 1, PFD, E>); break;
+        case 2: launch_dbg(gemm144_kernel<NSTAGE, 1, 2, PFD, E>); break;
+        case 4: launch_dbg(gemm144_kernel<NSTAGE, 1, 4, PFD, E>); break;
+        case 7: launch_dbg(gemm144_kernel<NSTAGE, 1, 7, PFD, E>); break;
+        default:
+          if (pf_on) launch_dbg(gemm144_kernel<NSTAGE, 1, 0, PFD, E>);
+          else launch_dbg(gemm144_kernel<NSTAGE, 1, 0, 0, E>);
+      }
+    };
+    if (epi) launch_exp(std::integral_constant<int, 1>{});
+    else launch_exp(std::integral_constant<int, 0>{});
     RGM_LAUNCH_CHECK();
     return RGM_OK;
   }
@@ -462,5 +610,14 @@ extern "C" int rgm_gemm144_dbg(int mode, long long* out64) {
     if (g_dbg144) (void)hipFree(g_dbg144);
     g_dbg144 = nullptr;
   }
+  return RGM_OK;
+}
+
+// the epilogue of the 128x144 kernel: 0 straight from the accumulators (four consumer waves), 1 whole rows through the ring (all eight
+// waves).  Same bits either way.  Returns the previous mode through *prev when given; a mode other than 0 / 1 is refused and changes nothing.
+extern "C" int rgm_set_gemm144_epilogue(int mode, int* prev) {
+  RGM_REQUIRE(mode == 0 || mode == 1, "set_gemm144_epilogue: %d (0 / 1)", mode);
+  if (prev) *prev = rgm::g_epi144;
+  rgm::g_epi144 = mode;
   return RGM_OK;
 }

@@ -113,6 +113,7 @@ def _load():
         "rgm_set_fuse_reduce_ln": (C.c_int, [i32]),
         "rgm_set_adaln_overlap": (C.c_int, [i32]),
         "rgm_set_dit_halves": (C.c_int, [i32, vp]),
+        "rgm_set_gemm144_epilogue": (C.c_int, [i32, vp]),
         "rgm_set_attn_pairs": (C.c_int, [i32]),
         "rgm_set_attn_stream": (C.c_int, [i32]),
         "rgm_set_attn_bwd_stream": (C.c_int, [i32]),

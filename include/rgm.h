@@ -447,6 +447,34 @@ int rgm_midi_read_scan(const uint8_t* blob, const int64_t* offsets, int N, long 
                        long long ccs_cap, void* ws, size_t ws_bytes, void* stream);
 int rgm_midi_read_rolls(int N, long long total_bytes, int total_tracks, double fs, long long start_column, int T, int out_u8, void* out,
                         int64_t* overflow, void* ws, size_t ws_bytes, void* stream);
+/* Audio of a roll on the device: the sine voice          the fork's pretty_midi/pretty_midi.py:954-983 (PrettyMIDI.synthesize, wave = np.sin) over
+ * pretty_midi/instrument.py:355-441 (Instrument.synthesize), applied to the notes and pedal events of piano_roll_to_pretty_midi
+ * (music_rule_guidance/piano_roll_to_chord.py:167-275); csrc/synth.hip, docs/rounds/synth.md.  The host partner is synthesize_roll.
+ * rgm_synth_render reads what rgm_midi_emit left on the device -- notes (rows of 4 int32, 16-byte aligned), ccs (rows of 2 int32), note_off /
+ *   cc_off (N) int64, counts (N,4) int64 of rgm_midi_measure; notes_rows / ccs_rows: rows the arrays hold, a sample whose rows lie outside
+ *   is rendered without them -- and four HOST tables, formed in float64 on the host so that every truncation is the host partner's own:
+ *   samp_host[k] = int(audio_fs * (k / fs)) and len_host[k] = int(audio_fs * (k / fs + 1)), T + 1 int64 each; omega_host[p] = 2 pi f_p * 1.0 /
+ *   audio_fs, 128 float64; fade_host = linspace(1, 0, F), F = int(.1 * audio_fs) <= cap / 8 + 16.  The integer tables must start at >= 0, not
+ *   decrease, stay below 2^31 and satisfy samp <= len; audio_fs must be positive: otherwise RGM_ERR_INVALID before any launch.  They are
+ *   copied on `stream` and must stay unchanged until those copies have run.
+ *   wave (N, cap) float64, 16-byte aligned: sample i of a row is the sum over the notes sounding there, in ascending pitch order, of
+ *   (((exp(-k / audio_fs) * fade) * velocity) * sin(omega[pitch] * k)), k = i - samp[start]; a note of n = samp[end] - samp[start] samples
+ *   fades over its last F samples by the table (n > F) or over all of them by linspace(1, 0, n) (n <= F); zero from the sample's length on.
+ *   cap: a multiple of 8, at least len_host[T].  lengths (N) int64 = len[last column holding a note end or a CC]; peak (N) float64 = the
+ *   largest magnitude; silent (N) int32 = 1 for a sample without notes or with a peak of 0 (the reference divides 0 by 0 there).
+ * rgm_synth_pcm: format 0: out (N, cap) float32 = (float)(wave / peak), the division in float64; format 1: out N WAV files (mono, 16 bit,
+ *   `rate` in the header) at a stride of 44 + 2 cap bytes, each with its own length in both size fields, samples (int16) rint((wave / peak) *
+ *   32767), zero bytes behind the file's end.  A silent sample gives zeros.  No host read between the two entries.
+ * ws: rgm_synth_workspace(N, T, cap) bytes (0 for sizes out of range: N 1 .. 65535, T 1 .. 32768, cap 8 .. 2^31 - 1), 16-byte aligned;
+ *   RGM_ERR_WORKSPACE if short.  Two launches + one; IEEE double without contraction, no atomics: bitwise repeatable, a sample's rows
+ *   independent of N and of its place in the batch. */
+size_t rgm_synth_workspace(int N, int T, long long cap);
+int rgm_synth_render(int N, int T, const int32_t* notes, long long notes_rows, const int64_t* note_off, const int32_t* ccs, long long ccs_rows,
+                     const int64_t* cc_off, const int64_t* counts, double audio_fs, const int64_t* samp_host, const int64_t* len_host,
+                     const double* omega_host, const double* fade_host, int F, double* wave, long long cap, int64_t* lengths, double* peak,
+                     int32_t* silent, void* ws, size_t ws_bytes, void* stream);
+int rgm_synth_pcm(int N, const double* wave, const int64_t* lengths, const double* peak, long long cap, int format, int rate, void* out,
+                  void* stream);
 /* Augmented training batches                              guided_diffusion/pr_datasets_all.py (ImageDataset.__getitem__, key_shift),
  * train_util.py (get_kl_input), compute_std.py; csrc/augment.hip; definition, quirks and measurements in docs/rounds/augment.md.
  *

@@ -147,6 +147,103 @@ def rolls_to_midi_bytes(roll_u8, fs=100, first_column_onsets=True, program=0):
     return [blob[int(e - s):int(e)] for s, e in zip(ev["sizes_host"][:, 3], ends)]
 
 
+WAV_BACKENDS = ("off", "device")
+_SYNTH_TABLES = {}
+
+
+def synth_host_tables(T, fs=100, audio_fs=44100):
+    """piano_roll_to_chord.synth_tables(T, fs, audio_fs), contiguous, read-only and cached per (T, fs, audio_fs): the host tables
+    rgm_synth_render copies on the caller's stream (they must outlive that copy, which the cache sees to).  ValueError for an fs /
+    audio_fs the tables refuse."""
+    from music_rule_guidance.piano_roll_to_chord import synth_tables
+    key = (int(T), fs, audio_fs)
+    tabs = _SYNTH_TABLES.get(key)
+    if tabs is None:
+        tabs = tuple(np.ascontiguousarray(t) for t in synth_tables(T, fs, audio_fs))
+        for t in tabs:
+            t.setflags(write=False)
+        if len(_SYNTH_TABLES) >= 64:
+            _SYNTH_TABLES.clear()
+        _SYNTH_TABLES[key] = tabs
+    return tabs
+
+
+def _synth_render(roll_u8, fs, audio_fs, first_column_onsets):
+    """-> (wave (N, cap) float64, lengths (N,) int64, peak (N,) float64, silent (N,) int32, cap): the render launches of csrc/synth.hip over
+    the note and CC rows csrc/midi.hip leaves on the device"""
+    from music_rule_guidance import music_rules
+    if not audio_fs > 0:
+        raise ValueError(f"audio_fs must be positive, got {audio_fs}")
+    ev = music_rules.midi_events_raw(roll_u8, fs=fs, first_column_onsets=first_column_onsets)
+    N = ev["counts"].shape[0]
+    T = music_rules._note_stats_layout(roll_u8)[3]
+    samp, length, omega, fade = synth_host_tables(T, fs, audio_fs)
+    cap = (int(length[T]) + 7) // 8 * 8
+    dev = ev["counts"].device
+    wave = torch.empty((N, cap), dtype=torch.float64, device=dev)
+    lengths = torch.empty(N, dtype=torch.int64, device=dev)
+    peak = torch.empty(N, dtype=torch.float64, device=dev)
+    silent = torch.empty(N, dtype=torch.int32, device=dev)
+    notes, ccs = ev["notes"], ev["ccs"]
+    with torch.cuda.device(dev):
+        nbytes = _rgm.lib.rgm_synth_workspace(N, T, cap)
+        if nbytes == 0:
+            raise ValueError(f"the device synthesiser does not serve {N} rolls of {T} columns with {cap} audio samples each")
+        ws = torch.empty((nbytes + 15) // 16 * 2, dtype=torch.int64, device=dev)
+        _rgm.check(_rgm.lib.rgm_synth_render(
+            N, T, _rgm.ptr(notes) if notes.numel() else None, notes.shape[0], _rgm.ptr(ev["note_offsets"]),
+            _rgm.ptr(ccs) if ccs.numel() else None, ccs.shape[0], _rgm.ptr(ev["cc_offsets"]), _rgm.ptr(ev["counts"]), float(audio_fs),
+            samp.ctypes.data, length.ctypes.data, omega.ctypes.data, fade.ctypes.data if len(fade) else None, len(fade), _rgm.ptr(wave), cap,
+            _rgm.ptr(lengths), _rgm.ptr(peak), _rgm.ptr(silent), _rgm.ptr(ws), ws.numel() * 8, _rgm.current_stream()))
+    return wave, lengths, peak, silent, cap
+
+
+def rolls_to_audio(roll_u8, fs=100, audio_fs=44100, first_column_onsets=True, normalize=True, dtype=torch.float32):
+    """uint8 device rolls in either layout rolls_to_midi_bytes takes -> (audio (N, cap) device tensor, lengths (N,) int64, silent (N,) bool):
+    row n holds, in its first lengths[n] entries, what the reference's piano_roll_to_pretty_midi(roll, fs) followed by its pretty_midi
+    fork's .synthesize(fs=audio_fs) returns for that roll -- every note one sine under exp(-t) with a 0.1 s linear fade-out, scaled by its
+    velocity, the sum divided by its largest magnitude -- and zeros behind; cap is the length a roll with an event in its last column
+    would have, rounded up to a multiple of 8.  Built by csrc/synth.hip; the host partner is piano_roll_to_chord.synthesize_roll.
+    normalize=False: the raw sum (Instrument.synthesize); dtype torch.float64 with normalize=False hands out the kernel's own rows.
+    ONE departure from the reference: a roll whose waveform is zero throughout (no notes, or none long enough to sound) gives zeros and
+    silent = True where the reference divides 0 by 0 and returns NaNs.  The rolls are not written to.  ValueError for an fs / audio_fs
+    the tables refuse (midi_tick_table, synth_host_tables)."""
+    if dtype not in (torch.float32, torch.float64):
+        raise ValueError(f"audio comes as torch.float32 or torch.float64, got {dtype}")
+    wave, lengths, peak, silent, cap = _synth_render(roll_u8, fs, audio_fs, first_column_onsets)
+    if not normalize:
+        audio = wave if dtype == torch.float64 else wave.to(dtype)
+    elif dtype == torch.float32:
+        audio = torch.empty((wave.shape[0], cap), dtype=torch.float32, device=wave.device)
+        with torch.cuda.device(wave.device):
+            _rgm.check(_rgm.lib.rgm_synth_pcm(wave.shape[0], _rgm.ptr(wave), _rgm.ptr(lengths), _rgm.ptr(peak), cap, 0, 0, _rgm.ptr(audio),
+                                              _rgm.current_stream()))
+    else:
+        audio = torch.where((peak > 0)[:, None], wave / peak.clamp_min(torch.finfo(torch.float64).tiny)[:, None], torch.zeros_like(wave))
+    return audio, lengths, silent.bool()
+
+
+def rolls_to_wav_bytes(roll_u8, fs=100, audio_fs=44100, first_column_onsets=True):
+    """uint8 device rolls -> a list of N `bytes`, each a mono 16-bit PCM WAV file of rolls_to_audio's normalised waveform: samples
+    rint(x * 32767) behind the 44-byte header the standard library's wave module writes (piano_roll_to_chord.wav_bytes of the same
+    waveform).  Rendered and quantised on the device without a host read in between, fetched with one device-to-host copy.  audio_fs
+    must be a whole number: it goes into the header."""
+    if int(audio_fs) != audio_fs:
+        raise ValueError(f"a WAV header holds a whole sample rate, got {audio_fs}")
+    wave, lengths, peak, silent, cap = _synth_render(roll_u8, fs, audio_fs, first_column_onsets)
+    N, stride = wave.shape[0], 44 + 2 * cap
+    out = torch.empty(N * stride, dtype=torch.uint8, device=wave.device)
+    with torch.cuda.device(wave.device):
+        _rgm.check(_rgm.lib.rgm_synth_pcm(N, _rgm.ptr(wave), _rgm.ptr(lengths), _rgm.ptr(peak), cap, 1, int(audio_fs), _rgm.ptr(out),
+                                          _rgm.current_stream()))
+    blob = out.cpu().numpy().tobytes()                  # the one copy out
+    files = []
+    for n in range(N):
+        size = 44 + int.from_bytes(blob[n * stride + 40:n * stride + 44], "little")      # 2 * lengths[n], from the file's own header
+        files.append(blob[n * stride:n * stride + size])
+    return files
+
+
 MIDI_READERS = ("host", "device")
 MIDI_READ_STATUS = {0: "accepted", 1: "not a Standard MIDI File", 2: "SMPTE or zero time division", 3: "bad or overrunning track chunk",
                     4: "data ends inside a message", 5: "data byte >= 0x80 in a channel message", 6: "more than 2048 tempo entries",
@@ -268,19 +365,25 @@ def read_midi_piano_roll_device(path, fs=100, columns=None):
     return midi_files_to_rolls([path], fs=fs, columns=columns, dtype=torch.float32)["roll"][0]
 
 
-def save_piano_roll_midi(sample, save_dir, fs=100, y=None, save_piano_roll=False, save_ind=0, midi_bytes=None):
+def save_piano_roll_midi(sample, save_dir, fs=100, y=None, save_piano_roll=False, save_ind=0, midi_bytes=None, wav_bytes=None):
     """sample: (B, 3, 128, T) uint8 array (or (B,128,T) / (B,2,128,T)).  Writes sample_<i>[_y_<label>].midi per sample (names
     and event extraction as in the reference :67-93, incl. the forced onsets in the first column) plus the raw roll as
     .npy; register_midi_writer replaces the built-in SMF writer.  save_piano_roll (PNG plots) is not provided.
     midi_bytes: a list of B finished files (rolls_to_midi_bytes of the same rolls while they were on the device) to write instead of running
-    the host extraction; a registered writer still takes precedence."""
+    the host extraction; a registered writer still takes precedence.
+    wav_bytes: a list of B finished WAV files (rolls_to_wav_bytes of the same rolls) written as sample_<i>[_y_<label>].wav beside the .midi."""
     from music_rule_guidance.piano_roll_to_chord import piano_roll_to_pretty_midi
     if midi_bytes is not None and len(midi_bytes) != sample.shape[0]:
         raise ValueError(f"midi_bytes holds {len(midi_bytes)} files for {sample.shape[0]} rolls")
+    if wav_bytes is not None and len(wav_bytes) != sample.shape[0]:
+        raise ValueError(f"wav_bytes holds {len(wav_bytes)} files for {sample.shape[0]} rolls")
     os.makedirs(save_dir, exist_ok=True)
     for i in range(sample.shape[0]):
         stem = f"sample_{i + save_ind}" + (f"_y_{int(y[i])}" if y is not None else "")
         np.save(os.path.join(save_dir, stem + ".npy"), sample[i])
+        if wav_bytes is not None:
+            with open(os.path.join(save_dir, stem + ".wav"), "wb") as f:
+                f.write(wav_bytes[i])
         if _MIDI_WRITER is not None:
             _MIDI_WRITER(sample[i], os.path.join(save_dir, stem + ".midi"), fs)
             continue

@@ -295,6 +295,82 @@ def piano_roll_to_pretty_midi(full_roll, fs=100, program=0):
     return pm
 
 
+# ---- sine synthesis of a roll: the host partner of csrc/synth.hip (docs/rounds/synth.md).  A restatement of the reference's vendored
+# pretty_midi fork -- PrettyMIDI.synthesize(fs, wave=np.sin) (pretty_midi/pretty_midi.py:954-983) over Instrument.synthesize
+# (pretty_midi/instrument.py:355-441), one instrument, no pitch bends, not a drum -- pinned to it bit for bit (tests/golden/synth.npz).
+def synth_tables(T, fs=100, audio_fs=44100):
+    """The four host tables the device renderer takes, all in float64 arithmetic so that every integer truncation and the phase increment
+    are synthesize_events' own bits: samp (T + 1,) int64 = int(audio_fs * (k / fs)), the first audio sample of column k; length (T + 1,)
+    int64 = int(audio_fs * (k / fs + 1)), the length of a waveform whose last event lies in column k; omega (128,) float64 =
+    2 pi f_p * 1.0 / audio_fs; fade = linspace(1, 0, int(.1 * audio_fs)).  ValueError unless fs and audio_fs are positive and every
+    entry stays below 2^31."""
+    T = int(T)
+    if T < 1:
+        raise ValueError(f"synthesis tables cover at least one column, got T = {T}")
+    if not fs > 0 or not audio_fs > 0 or not math.isfinite(audio_fs) or not math.isfinite(fs):
+        raise ValueError(f"fs and audio_fs must be positive, got {fs} and {audio_fs}")
+    if audio_fs * (T / fs + 1) >= 2.0 ** 31:
+        raise ValueError(f"a waveform of {T} columns at fs = {fs}, audio_fs = {audio_fs} would reach 2^31 samples")
+    t = np.arange(T + 1) / float(fs)                    # k / fs, the time of a note or event in column k
+    samp = (float(audio_fs) * t).astype(np.int64)       # int(): truncation of a non-negative float64
+    length = (float(audio_fs) * (t + 1)).astype(np.int64)
+    omega = np.array([2 * np.pi * (440.0 * (2.0 ** ((p - 69) / 12.0))) * 1.0 / audio_fs for p in range(128)], dtype=np.float64)
+    fade = np.linspace(1, 0, int(.1 * audio_fs))
+    return samp, length, omega, fade
+
+
+def synthesize_events(pm, audio_fs=44100):
+    """Instrument.synthesize(fs=audio_fs) of pm's one instrument: the un-normalised float64 sum of its notes' sines, L = int(audio_fs *
+    (end_time + 1)) samples, end_time counting the control changes.  Each note is wave = sin((2 pi f * 1.0 / audio_fs) * k + 0.0) for
+    k = 0 .. n - 1 under exp(-k / (1.0 * audio_fs)), the last int(.1 * audio_fs) samples (all of them for a note no longer than that)
+    under a linear fade to 0, times the velocity; notes are added in list order."""
+    ins = pm.instruments[0]
+    out = np.zeros(int(audio_fs * (pm.get_end_time() + 1)))
+    fade_out = np.linspace(1, 0, int(.1 * audio_fs))
+    for note in ins.notes:
+        start, end = int(audio_fs * note.start), int(audio_fs * note.end)
+        frequency = 440.0 * (2.0 ** ((note.pitch - 69) / 12.0))
+        k = np.arange(end - start)
+        wave = np.sin((2 * np.pi * frequency * 1.0 / audio_fs) * k + 0.0)
+        envelope = np.exp(-k / (1.0 * audio_fs))
+        if envelope.shape[0] > fade_out.shape[0]:
+            envelope[-fade_out.shape[0]:] *= fade_out
+        else:
+            envelope *= np.linspace(1, 0, envelope.shape[0])
+        envelope *= note.velocity
+        out[start:end] += envelope * wave
+    return out
+
+
+def synthesize_roll(full_roll, fs=100, audio_fs=44100, normalize=True, return_silent=False):
+    """(128,T), (2,128,T) or (3,128,T) roll -> float64 (L,): what the reference's piano_roll_to_pretty_midi(roll, fs) followed by its
+    fork's .synthesize(fs=audio_fs) returns (normalize=True: divided by its largest magnitude; False: Instrument.synthesize's raw sum).
+    Like piano_roll_to_pretty_midi this writes into full_roll.  ONE departure from the reference: a waveform that is zero throughout (a
+    roll without notes, or with notes too short to sound) is returned as zeros and reported silent, where the reference divides 0 by 0
+    and returns L NaNs.  return_silent: -> (waveform, silent)."""
+    out = synthesize_events(piano_roll_to_pretty_midi(full_roll, fs=fs), audio_fs)
+    peak = np.abs(out).max() if out.shape[0] else 0.0
+    silent = not peak > 0
+    if normalize and not silent:
+        out /= peak
+    return (out, silent) if return_silent else out
+
+
+def wav_bytes(x, audio_fs):
+    """A waveform in [-1, 1] -> the bytes of a mono 16-bit PCM RIFF file: samples rint(x * 32767) (halves to even) as int16 behind the
+    44-byte header the standard library's wave module writes."""
+    import io
+    import wave
+    pcm = np.rint(np.asarray(x, dtype=np.float64) * 32767).astype("<i2")
+    buf = io.BytesIO()
+    with wave.open(buf, "wb") as w:
+        w.setnchannels(1)
+        w.setsampwidth(2)
+        w.setframerate(int(audio_fs))
+        w.writeframes(pcm.tobytes())
+    return buf.getvalue()
+
+
 def quantize_pedal(value, num_bins=8):
     """pedal CC value 0..127 -> centre of its bin (reference midi_util.py:252-264: 0..15 -> 8, ..., 112..127 -> 120)."""
     if value < 0 or value > 127:

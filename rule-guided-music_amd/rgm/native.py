@@ -84,6 +84,10 @@ def _load():
         "rgm_midi_read_workspace": (sz, [i32, C.c_longlong, i32]),
         "rgm_midi_read_scan": (C.c_int, [vp, vp, i32, C.c_longlong, i32, C.c_double, vp, vp, vp, vp, vp, vp, C.c_longlong, vp, C.c_longlong, vp, sz, vp]),
         "rgm_midi_read_rolls": (C.c_int, [i32, C.c_longlong, i32, C.c_double, C.c_longlong, i32, i32, vp, vp, vp, sz, vp]),
+        "rgm_synth_workspace": (sz, [i32, i32, C.c_longlong]),
+        "rgm_synth_render": (C.c_int, [i32, i32, vp, C.c_longlong, vp, vp, C.c_longlong, vp, vp, C.c_double, vp, vp, vp, vp, i32, vp, C.c_longlong, vp, vp,
+                                       vp, vp, sz, vp]),
+        "rgm_synth_pcm": (C.c_int, [i32, vp, vp, vp, C.c_longlong, i32, i32, vp, vp]),
         "rgm_roll_augment_capacity": (C.c_int, [i32]),
         "rgm_roll_augment": (C.c_int, [vp, C.c_longlong, vp, vp, i32, vp, i32, i32, vp, vp, vp]),
         "rgm_latent_windows_count": (C.c_int, [i32, i32]),

@@ -34,6 +34,10 @@ def main(argv=None):
     parser.add_argument("--midi_backend", default="host", choices=list(midi_util.MIDI_BACKENDS),
                         help="'host': rank 0 extracts and writes the files one sample after the other at the end; 'device': rank 0 forms the "
                              "same bytes with csrc/midi.hip on the gathered device rolls of every round (docs/rounds/midi.md)")
+    parser.add_argument("--wav", default="off", choices=list(midi_util.WAV_BACKENDS),
+                        help="'device': a sample_<i>.wav beside every .midi, the roll's notes as sines rendered by csrc/synth.hip on rank 0 "
+                             "(mono, 16 bit; docs/rounds/synth.md); 'off': none")
+    parser.add_argument("--wav_fs", type=int, default=44100, help="audio samples per second of the .wav files")
     args = parser.parse_args(argv)
     from rgm import native as _native
     _native.set_gemm_precision(args.gemm_precision)
@@ -80,7 +84,8 @@ def main(argv=None):
     if args.use_dpmpp:
         sample_fn = partial(diffusion.dpmpp_sample_loop, order=int(args.dpmpp_order), eta=float(args.dpmpp_eta))
     device_midi = args.midi_backend == "device"
-    if (args.use_dpmpp or device_midi) and rank == 0:       # a default run writes no metadata file
+    device_wav = args.wav == "device"
+    if (args.use_dpmpp or device_midi or device_wav) and rank == 0:       # a default run writes no metadata file
         import json
         meta = {}
         if args.use_dpmpp:
@@ -88,9 +93,11 @@ def main(argv=None):
                                "order": int(args.dpmpp_order), "eta": float(args.dpmpp_eta)}
         if device_midi:
             meta["midi_backend"] = "device"
+        if device_wav:
+            meta["wav"], meta["wav_fs"] = "device", int(args.wav_fs)
         with open(os.path.join(save_dir, "run_metadata.json"), "w") as f:
             json.dump(meta, f, indent=1)
-    rolls, labels, midi_bytes = [], [], []
+    rolls, labels, midi_bytes, wav_files = [], [], [], []
     while len(rolls) * args.batch_size < args.num_samples:
         model_kwargs = {}
         classes = None
@@ -104,13 +111,17 @@ def main(argv=None):
         if device_midi and rank == 0:                       # every rank's rolls of this round, while they are on rank 0's device
             for g in gathered:
                 midi_bytes.extend(midi_util.rolls_to_midi_bytes(g, fs=args.fs, first_column_onsets=True))
+        if device_wav and rank == 0:
+            for g in gathered:
+                wav_files.extend(midi_util.rolls_to_wav_bytes(g, fs=args.fs, audio_fs=args.wav_fs, first_column_onsets=True))
         rolls.extend(g.cpu().numpy() for g in gathered)
         labels.extend(g.cpu().numpy() for g in gl)
         logger.log(f"created {len(rolls) * args.batch_size} samples")
 
     arr, label_arr = assemble(rolls, labels, args.num_samples)
     if rank == 0:
-        midi_util.save_piano_roll_midi(arr, save_dir, args.fs, y=label_arr, midi_bytes=midi_bytes[:len(arr)] if device_midi else None)
+        midi_util.save_piano_roll_midi(arr, save_dir, args.fs, y=label_arr, midi_bytes=midi_bytes[:len(arr)] if device_midi else None,
+                                       wav_bytes=wav_files[:len(arr)] if device_wav else None)
     if world > 1:
         dist.barrier()
     logger.log("sampling complete")

@@ -132,7 +132,7 @@ LAST_START = None      # the start latent of the last run under --edit_start ddi
 
 
 def main(argv=None):
-    args = _sr.add_midi_reader_arguments(_sr.add_midi_arguments(create_argparser())).parse_args(argv)
+    args = _sr.add_wav_arguments(_sr.add_midi_reader_arguments(_sr.add_midi_arguments(create_argparser()))).parse_args(argv)
     root = "edit_demo/"
     tail = args.config_path.split("configs/")[-1] if "configs/" in args.config_path else os.path.basename(args.config_path)
     args.dir = root + os.path.splitext(tail)[0] + f"_cls_{args.class_label}"
@@ -206,11 +206,13 @@ def main(argv=None):
         sample = midi_util.decode_sample_for_midi(sample, embed_model=embed_model, scale_factor=args.scale_factor, threshold=-0.95)
         note_cols = _sr.note_stats_columns(sample) if args.note_stats else {}                 # the whole saved roll, on the device
         midi_bytes = _sr.device_midi_bytes(sample, args) if args.save_files and rank0 else None   # the generated rolls only: the source stays on the host path
+        wav_files = _sr.device_wav_bytes(sample, args) if args.save_files and rank0 else None   # likewise: no audio of the source
         arr = sample.cpu().numpy().transpose(0, 3, 1, 2)
         arr_gt = ((gt + 1) * 63.5).clamp(0, 127).to(th.uint8).cpu().numpy()
         if args.save_files and rank0:
             lab = classes.cpu().numpy() if classes is not None else None
-            midi_util.save_piano_roll_midi(arr, save_dir, args.fs, y=lab, save_ind=count_samples, midi_bytes=midi_bytes)
+            midi_util.save_piano_roll_midi(arr, save_dir, args.fs, y=lab, save_ind=count_samples, midi_bytes=midi_bytes,
+                                           wav_bytes=wav_files)
             midi_util.save_piano_roll_midi(arr_gt, save_dir_gt, args.fs, y=lab[:1] if lab is not None else None, save_ind=count_samples)
         generated = th.from_numpy(arr.astype(np.float32)) / 63.5 - 1
         generated = generated[:, :, :, edit_kwargs["l_start_pix"]:edit_kwargs["l_end_pix"]]   # only the edited excerpt is scored

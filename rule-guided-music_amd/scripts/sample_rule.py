@@ -112,6 +112,8 @@ def write_run_metadata(save_dir, args, extra=None):
     meta["long_backward"] = bool(long_backward())     # RGM_LONG_BACKWARD / set_long_backward: guidance beyond 256 / 288 tokens was allowed
     meta["particles"] = particle_metadata(args)       # --particles: the particle loop in place of the SCG search (docs/rounds/particles.md)
     meta["midi_backend"] = getattr(args, "midi_backend", "host")    # who wrote the .midi files: the host loop or csrc/midi.hip (docs/rounds/midi.md)
+    meta["wav"] = getattr(args, "wav", "off")         # .wav files beside the .midi: csrc/synth.hip's sine voice (docs/rounds/synth.md)
+    meta["wav_fs"] = getattr(args, "wav_fs", 44100) if meta["wav"] != "off" else None
     meta.update(extra or {})
     with open(os.path.join(save_dir, "run_metadata.json"), "w") as f:
         json.dump(meta, f, indent=1)
@@ -139,6 +141,14 @@ def device_midi_bytes(sample_u8, args):
     if getattr(args, "midi_backend", "host") != "device":
         return None
     return midi_util.rolls_to_midi_bytes(sample_u8, fs=args.fs, first_column_onsets=True)
+
+
+def device_wav_bytes(sample_u8, args):
+    """--wav device: one finished .wav per uint8 roll, rendered and quantised on the device before the rolls are copied down; the audio
+    holds the notes of the .midi written beside it (first-column onsets set); None under --wav off."""
+    if getattr(args, "wav", "off") != "device":
+        return None
+    return midi_util.rolls_to_wav_bytes(sample_u8, fs=args.fs, audio_fs=args.wav_fs, first_column_onsets=True)
 
 
 def summary_columns(all_results):
@@ -366,7 +376,7 @@ def build_pipeline(args, config, device):
 
 
 def main(argv=None):
-    args = add_midi_arguments(add_particle_arguments(add_note_stats_arguments(add_sampler_arguments(create_argparser())))).parse_args(argv)
+    args = add_wav_arguments(add_midi_arguments(add_particle_arguments(add_note_stats_arguments(add_sampler_arguments(create_argparser()))))).parse_args(argv)
     args.dir = output_dir_for(args.config_path, args.class_label)
     from rgm import native as _native
     _native.set_gemm_precision(args.gemm_precision)      # "bf16x3_presplit" / "bf16x3" (fast, fp32-grade) or "fp32" (exact fp32 MFMA)
@@ -432,10 +442,12 @@ def main(argv=None):
         sample = midi_util.decode_sample_for_midi(sample, embed_model=embed_model, scale_factor=args.scale_factor, threshold=-0.95)
         note_cols = note_stats_columns(sample) if args.note_stats else {}                  # on the device, before the roll leaves it
         midi_bytes = device_midi_bytes(sample, args) if args.save_files and rank0 else None
+        wav_files = device_wav_bytes(sample, args) if args.save_files and rank0 else None
         arr = sample.cpu().numpy().transpose(0, 3, 1, 2)                                   # (B, 3, 128, T) uint8
         if args.save_files and rank0:
             midi_util.save_piano_roll_midi(arr, save_dir, args.fs, y=classes_of.cpu().numpy() if classes_of is not None else None,
-                                           save_ind=count_samples * (arr.shape[0] // args.batch_size), midi_bytes=midi_bytes)
+                                           save_ind=count_samples * (arr.shape[0] // args.batch_size), midi_bytes=midi_bytes,
+                                           wav_bytes=wav_files)
         generated = th.from_numpy(arr.astype(np.float32)) / 63.5 - 1
         results = midi_util.eval_rule_loss(generated, rules_of)
         for name, col in list(note_cols.items()) + list(particle_cols.items()):
@@ -512,6 +524,17 @@ def add_midi_arguments(parser):
     g.add_argument("--midi_backend", default="host", choices=list(midi_util.MIDI_BACKENDS),
                    help="'host': piano_roll_to_pretty_midi and SimpleMIDI.write, one sample after the other; 'device': the same bytes formed by "
                         "csrc/midi.hip for the whole batch while the rolls are still on the device (fs <= 220)")
+    return parser
+
+
+def add_wav_arguments(parser):
+    """--wav and --wav_fs: audio beside the .midi files, shared by sample_rule.py and edit.py (cfg_sample.py adds the same two flags; kept
+    out of create_argparser's defaults and in a group of their own like --midi_backend; docs/rounds/synth.md)."""
+    g = parser.add_argument_group("audio")
+    g.add_argument("--wav", default="off", choices=list(midi_util.WAV_BACKENDS),
+                   help="'device': a sample_<i>.wav beside every .midi, the roll's notes as sines rendered by csrc/synth.hip (mono, 16 bit; "
+                        "docs/rounds/synth.md); 'off': none")
+    g.add_argument("--wav_fs", type=int, default=44100, help="audio samples per second of the .wav files")
     return parser
 
 

@@ -71,7 +71,7 @@ def note_density(roll, interval=128, horizontal_scale=5):
     n, T = pr.shape[0], pr.shape[-1]
     pr[pr < F32(-0.95)] = -1.0                        # in place, like the reference
     b = (pr + 1) / F32(2.0)
-    b = (b >= F32(1e-2)).astype(F32)
+    b = np.where(b >= F32(1e-2), F32(1), np.where(b < F32(1e-2), F32(0), b)).astype(F32)   # a NaN cell passes both masks and stays NaN
     vert_col = b.sum(axis=2, dtype=F32)               # (N,1,T)
     bp = np.pad(b, ((0, 0), (0, 0), (0, 0), (1, 1)))
     d = np.diff(bp, axis=-1)

@@ -78,6 +78,7 @@ extern "C" int rgm_collage_split(const float* img, float* wins, float* halves, i
   RGM_REQUIRE(img && wins && B > 0 && C > 0 && h > 0 && n > 0 && overlap >= 0 && overlap < BASE, "collage_split: bad arguments");
   const int stride = BASE - overlap;
   RGM_REQUIRE((n - 1) * stride + BASE <= W + overlap, "collage_split: %d windows do not fit width %d", n, W);
+  RGM_REQUIRE(overlap <= W, "collage_split: the circular extension of %d columns is wider than the image (%d)", overlap, W);   // one wrap only
   const long long total = (long long)B * n * C * h * BASE;
   hipLaunchKernelGGL(collage_split_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, img, wins, halves,
                      B, C, h, W, n, stride, overlap);
@@ -89,6 +90,8 @@ extern "C" int rgm_collage_merge(const float* full, const float* half, float* ou
                                  int circle, int is_avg, void* stream) {
   RGM_REQUIRE(full && out && B > 0 && C > 0 && h > 0 && n > 0 && overlap >= 0 && overlap < BASE, "collage_merge: bad arguments");
   const int Wl = n * BASE - (n - 1) * overlap;
+  RGM_REQUIRE(!circle || overlap <= Wl - overlap, "collage_merge: the circular seam of %d columns is wider than the image (%d)", overlap,
+              Wl - overlap);   // rgm_collage_split refuses the same shape
   const long long total = (long long)B * C * h * (circle ? Wl - overlap : Wl);
   hipLaunchKernelGGL(collage_merge_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, full, half, out, B,
                      C, h, n, overlap, circle, is_avg);

@@ -59,6 +59,8 @@ __global__ __launch_bounds__(256) void note_density_kernel(float* __restrict__ r
   __shared__ int vcnt[256], hcnt[256];
   const int n = blockIdx.y, t = blockIdx.x * 256 + threadIdx.x;
   float* base = roll + (long long)n * C * 128 * T;
+  // A NaN cell passes both of the reference's binarisation masks (music_rules.py:65-69) and stays NaN: the column's count is NaN, and so
+  // are the two differences it enters, which flag its own column and the next as onsets.  bit 16 of v marks a column that holds one.
   int v = 0, on = 0;
   if (t < T) {
     for (int p = 0; p < 128; ++p) {
@@ -69,10 +71,12 @@ __global__ __launch_bounds__(256) void note_density_kernel(float* __restrict__ r
       }
       const float x = row[t];
       const bool act = !(x < -0.95f);                    // x<-0.95 -> -1 -> 0 ; everything else >= 0.025 -> 1
-      const bool prev = t > 0 ? !(row[t - 1] < -0.95f) : false;   // zero pad on the left; value is threshold-stable
+      const float xp = t > 0 ? row[t - 1] : -1.0f;
+      const bool prev = t > 0 ? !(xp < -0.95f) : false;   // zero pad on the left; value is threshold-stable
       if (!act) row[t] = -1.0f;
       v += act ? 1 : 0;
-      on |= (act && !prev) ? 1 : 0;
+      if (x != x) v |= 1 << 16;
+      on |= ((act && !prev) || x != x || xp != xp) ? 1 : 0;
     }
   }
   vcnt[threadIdx.x] = v;
@@ -88,20 +92,20 @@ __global__ __launch_bounds__(256) void note_density_kernel(float* __restrict__ r
         sv += vcnt[threadIdx.x * interval + k];
         shh += hcnt[threadIdx.x * interval + k];
       }
-      out[(long long)n * 2 * nwin + w] = (float)sv / (float)interval;
+      out[(long long)n * 2 * nwin + w] = (sv >> 16) ? __builtin_nanf("") : (float)sv / (float)interval;   // counts stay below 2^16
       out[(long long)n * 2 * nwin + nwin + w] = (float)shh / hscale;
     }
   }
 }
 
-// torch.bucketize(v, bounds) (right=False): first index i with bounds[i] >= v ; out int64
+// torch.bucketize(v, bounds) (right=False): first index i with bounds[i] >= v ; NaN compares above every bound -> nb ; out int64
 __global__ void bucketize_kernel(const float* __restrict__ v, const float* __restrict__ bounds, int nb, int64_t* __restrict__ out,
                                  int n) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   const float x = v[i];
   int k = 0;
-  while (k < nb && bounds[k] < x) ++k;
+  while (k < nb && !(bounds[k] >= x)) ++k;
   out[i] = k;
 }
 
@@ -110,13 +114,15 @@ __global__ void row_loss_kernel(const float* __restrict__ a, const float* __rest
                                 int zero_one) {
   const int r = blockIdx.x * blockDim.x + threadIdx.x;
   if (r >= rows) return;
-  float s = 0.f;
+  // The squared differences are summed in double, which rounds far below float32, and the mean is rounded to float once: a float sum
+  // rounds x - y, its square and every addition, 3 x 2^-24 of the result at K = 1.  The counts of the zero-one loss are exact either way.
+  double s = 0.0;
   for (int k = 0; k < K; ++k) {
     const float x = a[(long long)r * K + k], y = b[(long long)r * K + k];
-    if (zero_one) s += (x != y) ? 1.f : 0.f;
-    else { const float d = x - y; s += d * d; }
+    if (zero_one) s += (x != y) ? 1.0 : 0.0;
+    else { const double d = (double)x - (double)y; s += d * d; }
   }
-  out[r] = s / (float)K;
+  out[r] = zero_one ? (float)s / (float)K : (float)(s / (double)K);
 }
 // DPS through the differentiable pitch histogram (condition_functions.py:122-126 rule_x0_mse_dummy on music_rules.py:29-43):
 // one thread per sample: hist as pitch_fold_kernel, logp = -scale * sum (hist - target)^2 and
